@@ -21,6 +21,9 @@ sequence is loaded again (parameters, Adam moments and step counter back to thei
 and K timed steps are exactly the first W + K iterations of the fit; ``ramp_iterations`` is reported in the line.
 The one-off host costs of the result path (first ``params72`` / all-gather call load their kernels lazily, 0.5 ms) are
 paid during the ramp as well.
+``--dump-outputs DIR`` writes, after the timed window, what the timed path computed in its last step as DIR/<name>.npy (the
+fitted rows, parameters, losses, vertices and joints; float32, 14 MB at B = 119): the inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -496,6 +499,38 @@ def ae_probe(device):
             'workload': 'models/AE.py infilling autoencoder, [1,4,210,135] clip image, masked L1, Adam 3e-6 (opt_amass_temp.py:154-214)'}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(arrays):
+    """--dump-outputs, first half: host copies (float32 / float64) of what the timed path handed its caller after its last step,
+    taken right after the timed window -- the probes that follow reuse the engine's buffers"""
+    out = {}
+    for name, a in arrays.items():
+        a = np.array(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT_BYTES, f'--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}'
+    return out
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs, second half: DIR/<name>.npy per array"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
+def fit_outputs(fit, gathered, losses):
+    """what a caller of the AMASS fit receives after step(K): the fitted rows of every rank (body_params_opt_t_72, [world, B, 72]),
+    the live parameters after the last update ([B, 75]: transl, rot6d, betas, z + hands), the loss terms and vertices / posed joints
+    of the last forward"""
+    from lemo_amd.fitting import LOSS_NAMES
+    out = {'params72': gathered, 'params75': fit.params75(), 'vertices': fit.vertices(), 'joints': fit.posed_joints()}
+    out.update({'loss_' + k: np.float32(losses[k]) for k in LOSS_NAMES})
+    return host_outputs(out)
+
+
 def timed_fit(fit, prob, stream, device, steps=100, warmup=10):
     """iterations/s of a fresh fit over `steps` timed steps after `warmup` (graphs prepared before, result read inside the window)"""
     fit.load_sequence(prob['seq']['init_params'], prob['markers'], prob['seq']['contact_lbl'])
@@ -614,6 +649,9 @@ def main_prox(args, world, rank, device):
         if r != rank:
             assert not torch.equal(gathered[r], local), 'ranks fitted the same recording'
     assert eng.nonfinite_step() == 0
+    if args.dump_outputs and rank == 0:
+        # the fitted rows of every rank ([world, B, 81], ENGINE_PARAMS order) and the loss record of the last closure (LOSS_KEYS)
+        write_outputs(args.dump_outputs, host_outputs(dict({'params': gathered}, **{k: np.float32(v) for k, v in eng.loss_dict().items()})))
     out = {'metric': 'PROX fitting-iterations/sec (100-frame window, PROXD_temp_S3)', 'value': world * args.steps / dt,
            'unit': 'fitting-iterations/s', 'n_gpus': world, 'steps': args.steps, 'warmup': n_warm,
            'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32',
@@ -658,6 +696,9 @@ def main():
     ap.add_argument('--concurrent-clips', type=int, default=3,
                     help='after the headline measurement (one clip per GPU), also time this many independent clips fitted side by '
                          'side on GPU 0 (reported as "concurrent_clips", never as "value"; 0 = off)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / '
+                         'float64, rank 0; the inputs are seeded: the same arguments give the same inputs on every run)')
     args = ap.parse_args()
     if args.model == 'coherent':
         from lemo_amd import synthetic as _syn
@@ -767,6 +808,8 @@ def main():
             assert not torch.equal(gathered[r], local72), f'rank {r} returned the same fit as rank {rank}: sequences not sharded'
     assert bool(torch.isfinite(gathered).all()) and fit.nonfinite_step() == 0
     losses = fit.losses()
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, fit_outputs(fit, gathered, losses))
     if args.emu:
         out = {'metric': 'fitting-iterations/sec (T=120 frames)', 'value': world * args.steps / dt, 'unit': 'fitting-iterations/s',
                'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True,

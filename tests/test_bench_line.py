@@ -31,3 +31,54 @@ def test_default_variant_label_is_split_f16():
     from lemo_amd.priors import DEFAULT_CONV_VARIANT
     assert b.DEFAULT_CONV_VARIANT == DEFAULT_CONV_VARIANT
     assert 'split-f16' in b.arithmetic_label(DEFAULT_CONV_VARIANT)
+
+
+def _bench_dump(out_dir, steps, warmup, extra=()):
+    """``bench.py --gpus 1 --emu --steps K --warmup W --dump-outputs DIR`` (the host-emulated library): the JSON line and the arrays"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    subprocess.run(['make', '-C', os.path.join(ROOT, 'lemo_amd', 'csrc'), '-j8', 'emu'], check=True, capture_output=True)
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--emu', '--backend', 'gloo', '--steps', str(steps),
+           '--warmup', str(warmup), '--dump-outputs', str(out_dir)] + list(extra)
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(env, OMP_NUM_THREADS='2'))
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+
+
+@pytest.mark.timeout(900)
+def test_dump_outputs_hold_the_last_timed_step(tmp_path, emu_lib):
+    """--dump-outputs writes what the timed path computed in its last step (float32 / float64, at most 64 MB), the same arguments give
+    the same arrays, and --steps K after --warmup W is exactly W + K iterations of the fit"""
+    import numpy as np
+    d, a = _bench_dump(tmp_path / 'a', 3, 1)
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0
+    assert {'params72', 'params75', 'vertices', 'joints', 'loss_total'} <= set(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert float(a['loss_total']) == np.float32(d['final_total_loss'])
+    _, b = _bench_dump(tmp_path / 'b', 3, 1)
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    # the same fit in this process: W warm-up + K timed iterations from the seeded start
+    fit, _, B = _bench().build_problem_emu(0)
+    fit.step(1, use_graph=False)
+    fit.step(3, use_graph=False)
+    assert a['params72'].shape == (1, B, 72)
+    assert np.array_equal(a['params72'][0], fit.params72().numpy())
+    assert np.array_equal(a['params75'], fit.params75().numpy())
+    assert np.array_equal(a['vertices'], fit.vertices().numpy())
+    fit.step(1, use_graph=False)
+    assert not np.array_equal(a['params72'][0], fit.params72().numpy())      # one more step is visible
+
+
+@pytest.mark.timeout(900)
+def test_dump_outputs_prox_workload(tmp_path, emu_lib):
+    import numpy as np
+    d, a = _bench_dump(tmp_path / 'p', 2, 1, ['--workload', 'prox'])
+    assert d['steps'] == 2 and d['ms_per_step'] > 0
+    assert a['params'].shape[0] == 1 and a['params'].dtype == np.float32 and np.isfinite(a['params']).all()
+    assert float(a['total_loss']) == np.float32(d['total_loss'])
