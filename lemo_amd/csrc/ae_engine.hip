@@ -503,16 +503,13 @@ ae_conv16_f16_kernel(const float* __restrict__ in, const float* __restrict__ wt,
 }
 
 
-static int ae_conv_init() {
-  static int rc = -1;
-  if (rc >= 0) return rc;
-  rc = 0;
-#define OPTIN(K_) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&K_), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); if (e != hipSuccess) rc = (int)e; }
-  OPTIN((ae_conv_kernel<1, 0>)) OPTIN((ae_conv_kernel<1, 1>)) OPTIN((ae_conv_kernel<1, 2>)) OPTIN((ae_conv_kernel<2, 0>)) OPTIN((ae_conv_kernel<2, 1>)) OPTIN((ae_conv_kernel<2, 2>))
-  OPTIN((ae_conv_f16_kernel<1, 0>)) OPTIN((ae_conv_f16_kernel<1, 1>)) OPTIN((ae_conv_f16_kernel<1, 2>))
-  OPTIN((ae_conv_f16_kernel<2, 0>)) OPTIN((ae_conv_f16_kernel<2, 1>)) OPTIN((ae_conv_f16_kernel<2, 2>))
-#undef OPTIN
-  return rc;
+int ae_conv_init() {
+  static LdsOptinOnce once;
+  constexpr int B = 64 * 1024;
+  return lds_optin(once, {{&ae_conv_kernel<1, 0>, B}, {&ae_conv_kernel<1, 1>, B}, {&ae_conv_kernel<1, 2>, B},
+                          {&ae_conv_kernel<2, 0>, B}, {&ae_conv_kernel<2, 1>, B}, {&ae_conv_kernel<2, 2>, B},
+                          {&ae_conv_f16_kernel<1, 0>, B}, {&ae_conv_f16_kernel<1, 1>, B}, {&ae_conv_f16_kernel<1, 2>, B},
+                          {&ae_conv_f16_kernel<2, 0>, B}, {&ae_conv_f16_kernel<2, 1>, B}, {&ae_conv_f16_kernel<2, 2>, B}});
 }
 
 // Launch shape: tile (mt = 2: 32 px x 64 cout, 1: 32 x 32, 3: 16 x 16), pixel tiles per workgroup PT and K slices KS

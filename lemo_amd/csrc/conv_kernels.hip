@@ -485,18 +485,14 @@ conv3x3_mfma_v2_kernel(const float* __restrict__ in, const float* __restrict__ w
   }
 }
 
-// > 64 KB of dynamic LDS needs an explicit opt-in per kernel (once per process; never inside a capture
-// because lemo_fit_create / the first eager call runs it first)
+// > 64 KB of dynamic LDS: opted in once per device (kernels.hpp: lds_optin; the engines' create functions run it before any capture)
 int conv_lds_init() {
-  static int rc = -1;
-  if (rc >= 0) return rc;
-  rc = 0;
-#define OPTIN(EPI_, NT_, DBG_) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_mfma_v2_kernel<EPI_, NT_, 2, DBG_>), hipFuncAttributeMaxDynamicSharedMemorySize, Cv2Cfg<NT_, 2>::SMEM_BYTES); if (e != hipSuccess) rc = (int)e; }
-  OPTIN(0, 512, false) OPTIN(1, 512, false) OPTIN(2, 512, false)
-  OPTIN(0, 256, false) OPTIN(1, 256, false) OPTIN(2, 256, false)
-  OPTIN(0, 512, true)
-#undef OPTIN
-  return rc;
+  static LdsOptinOnce once;
+  constexpr int B512 = Cv2Cfg<512, 2>::SMEM_BYTES, B256 = Cv2Cfg<256, 2>::SMEM_BYTES;
+  return lds_optin(once, {{&conv3x3_mfma_v2_kernel<0, 512, 2, false>, B512}, {&conv3x3_mfma_v2_kernel<1, 512, 2, false>, B512},
+                          {&conv3x3_mfma_v2_kernel<2, 512, 2, false>, B512}, {&conv3x3_mfma_v2_kernel<0, 256, 2, false>, B256},
+                          {&conv3x3_mfma_v2_kernel<1, 256, 2, false>, B256}, {&conv3x3_mfma_v2_kernel<2, 256, 2, false>, B256},
+                          {&conv3x3_mfma_v2_kernel<0, 512, 2, true>, B512}});
 }
 
 int conv3x3_mfma_lds(const float* in, const float* wt, const float* wt2, const float* bias, const float* aux, float* out,
@@ -510,7 +506,7 @@ int conv3x3_mfma_lds(const float* in, const float* wt, const float* wt2, const f
   const int units = ((rem + 15) / 16) * (cpb / 16);
   const int tailb = units;                                       // one 16x16 unit per tail block
   dim3 grid(full + tailb, cout / cpb);
-  conv_lds_init();
+  if (int rc = conv_lds_init()) return rc;
   if (dbg) {                                 // census build of the forward 64-cout kernel (tools/conv_census.py)
     if (cpb != 64 || epi != 0) return LEMO_ERR_ARG;
     hipLaunchKernelGGL((conv3x3_mfma_v2_kernel<0, 512, 2, true>), grid, dim3(512), (Cv2Cfg<512, 2>::SMEM_BYTES), s, in, wt, wt2, bias, aux, out, H, W, cin / 8, cout, full, tailb, dbg);

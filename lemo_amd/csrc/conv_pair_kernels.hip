@@ -450,14 +450,9 @@ conv3x3_pair_kernel(PairArgs a) {
   }
 }
 
-static int conv_pair_init() {
-  static int rc = -1;
-  if (rc >= 0) return rc;
-  rc = 0;
-#define OPTIN(EPI_, DBG_) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pair_kernel<EPI_, DBG_>), hipFuncAttributeMaxDynamicSharedMemorySize, CP_SMEM); if (e != hipSuccess) rc = (int)e; }
-  OPTIN(0, false) OPTIN(1, false) OPTIN(0, true)
-#undef OPTIN
-  return rc;
+int conv_pair_init() {
+  static LdsOptinOnce once;
+  return lds_optin(once, {{&conv3x3_pair_kernel<0, false>, CP_SMEM}, {&conv3x3_pair_kernel<1, false>, CP_SMEM}, {&conv3x3_pair_kernel<0, true>, CP_SMEM}});
 }
 
 bool conv3x3_pair_supported(int H, int W, int c0, int c1, int c2) {

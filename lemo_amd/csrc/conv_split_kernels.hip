@@ -445,16 +445,13 @@ conv3x3_split_kernel(const float* __restrict__ in, const uint4* __restrict__ w3,
 }
 
 int conv_split_init() {
-  static int rc = -1;
-  if (rc >= 0) return rc;
-  rc = 0;
-#define OPTIN(EPI_, CI_, CO_, NP_, DBG_) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_split_kernel<EPI_, CI_, CO_, NP_, DBG_>), hipFuncAttributeMaxDynamicSharedMemorySize, (Cv3Cfg<CI_, CO_, NP_>::SMEM_BYTES)); if (e != hipSuccess) rc = (int)e; }
-#define OPTIN3(CI_, CO_, NP_) OPTIN(0, CI_, CO_, NP_, false) OPTIN(1, CI_, CO_, NP_, false) OPTIN(2, CI_, CO_, NP_, false)
-  OPTIN3(64, 64, 3) OPTIN3(64, 32, 3) OPTIN3(32, 64, 3) OPTIN3(32, 32, 3) OPTIN(0, 64, 64, 3, true)
-  OPTIN3(64, 64, 2) OPTIN3(64, 32, 2) OPTIN3(32, 64, 2) OPTIN3(32, 32, 2) OPTIN(0, 64, 64, 2, true)
-#undef OPTIN3
-#undef OPTIN
-  return rc;
+  static LdsOptinOnce once;
+#define E(EPI_, CI_, CO_, NP_, DBG_) {&conv3x3_split_kernel<EPI_, CI_, CO_, NP_, DBG_>, Cv3Cfg<CI_, CO_, NP_>::SMEM_BYTES}
+#define E3(CI_, CO_, NP_) E(0, CI_, CO_, NP_, false), E(1, CI_, CO_, NP_, false), E(2, CI_, CO_, NP_, false)
+  return lds_optin(once, {E3(64, 64, 3), E3(64, 32, 3), E3(32, 64, 3), E3(32, 32, 3), E(0, 64, 64, 3, true),
+                          E3(64, 64, 2), E3(64, 32, 2), E3(32, 64, 2), E3(32, 32, 2), E(0, 64, 64, 2, true)});
+#undef E3
+#undef E
 }
 
 // shapes the split kernel takes; everything else stays on conv3x3_mfma_lds

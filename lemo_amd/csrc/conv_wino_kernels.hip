@@ -294,14 +294,9 @@ conv3x3_wino_kernel(WinoArgs a) {
   }
 }
 
-static int conv_wino_init() {
-  static int rc = -1;
-  if (rc >= 0) return rc;
-  rc = 0;
-#define OPTIN(EPI_, DBG_) { hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<EPI_, DBG_>), hipFuncAttributeMaxDynamicSharedMemorySize, WN_SMEM); if (e != hipSuccess) rc = (int)e; }
-  OPTIN(0, false) OPTIN(1, false) OPTIN(0, true)
-#undef OPTIN
-  return rc;
+int conv_wino_init() {
+  static LdsOptinOnce once;
+  return lds_optin(once, {{&conv3x3_wino_kernel<0, false>, WN_SMEM}, {&conv3x3_wino_kernel<1, false>, WN_SMEM}, {&conv3x3_wino_kernel<0, true>, WN_SMEM}});
 }
 
 bool conv3x3_wino_supported(int H, int W, int cin, int cout) {

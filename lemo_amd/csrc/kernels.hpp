@@ -5,8 +5,34 @@
 #include "lemo_hip.h"
 
 #include <cmath>
+#include <initializer_list>
+#include <mutex>
 
 namespace lemo {
+
+// ---------------- lemo_hip.hip: the dynamic-LDS opt-in ----------------
+// A launch with more than 64 KiB of dynamic LDS needs its function's MaxDynamicSharedMemorySize attribute raised first, on the
+// device it runs on.  Each kernel family lists its (kernel, bytes) pairs in one <family>_init(); lds_optin runs such a list once per
+// current device (devices 0 .. 63), race-free: it checks every size against the device's LDS per workgroup, sets the attributes
+// and caches the result (0 or the hipError_t) for that device.  lds_init_all() runs every family's list: lemo_fit_create and
+// lemo_prox_create call it (lemo_ae_create runs ae_conv_init, the only family its engine launches), so no engine's first opt-in
+// happens inside a graph capture.  The launchers still call their own family's init (a cheap fast path), for C-ABI callers that
+// launch without an engine.
+struct LdsOptin {
+  const void* fn;
+  int bytes;
+  template <typename F> LdsOptin(F* kernel, int b) : fn(reinterpret_cast<const void*>(kernel)), bytes(b) {}
+};
+struct LdsOptinOnce { std::once_flag flag[64]; int rc[64]; };      // one per family, static
+int lds_optin(LdsOptinOnce& once, std::initializer_list<LdsOptin> tab);
+int lds_init_all();
+int conv_lds_init();
+int conv_split_init();
+int conv_pair_init();
+int conv_wino_init();
+int enc_tail3_init();
+int lbs_init();
+int ae_conv_init();
 
 // The reference writes its learning rates as decimal literals (0.01, 0.005, 0.1, 0.003, 3e-6: Python doubles) and torch divides
 // THAT double by the bias correction; the C ABI carries them as float.  The shortest decimal (<= 6 significant digits) that
@@ -25,14 +51,12 @@ int conv3x3_mfma_splitk(const float* in, const float* wt, const float* bias, con
                         int H, int W, int cin, int cout, int epi, hipStream_t s);
 int conv3x3_mfma_lds(const float* in, const float* wt, const float* wt2, const float* bias, const float* aux, float* out,
                      int H, int W, int cin, int cout, int epi, hipStream_t s, unsigned long long* dbg = nullptr);
-int conv_lds_init();
 // ---------------- conv_split_kernels.hip ----------------
 // variant 3: fp32-exact 64->64 conv on the bf16 matrix cores (3-way bf16 operand split, 6 products)
 bool conv3x3_split_supported(int H, int W, int cin, int cout);
 int conv3x3_mfma_split(const float* in, const void* w3, const float* wt, const float* bias, const float* aux, float* out,
                        int H, int W, int cin, int cout, int epi, hipStream_t s, unsigned long long* dbg = nullptr, int pieces = 3,
                        float winv = 1.f);
-int conv_split_init();
 // ---------------- conv_pair_kernels.hip ----------------
 // variant 5: TWO 64 -> 64 layers per launch on 10 x 14 tiles, intermediate in LDS (split-f16 arithmetic of variant 4)
 bool conv3x3_pair_supported(int H, int W, int c0, int c1, int c2);
@@ -103,7 +127,6 @@ int smplx_pose_fwd(const BodyConst& c, const PoseIn& in, const PoseWs& ws, int B
 int smplx_pose_bwd(const BodyConst& c, const PoseWs& ws, const PoseGradIn& gi, const PoseGradOut& go, int B, hipStream_t s);
 
 // ---------------- lbs_kernels.hip ----------------
-int lbs_init();
 // verts[b][slot] for slot < n ; ids == null => slot == vertex id, n == V
 int lbs_verts_fwd_active(const SkinConst& c, const VertexSetBwd& u, const float* Xg, int Bp, const float* A, int nj,
                          const float* transl, int B, float* blend, float* verts, float* v_posed, hipStream_t s, float* transl_copy = nullptr);

@@ -492,17 +492,12 @@ lbs_verts_fwd_kernel(SkinConst c, const float* __restrict__ Xg, int Bp, const fl
 }
 
 int lbs_init() {
-  static int rc = -1;
-  if (rc >= 0) return rc;
-  rc = 0;
-#define OPTIN(DBG_, SPLIT_, PRE_) if (!rc) rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_verts_fwd_kernel<DBG_, SPLIT_, PRE_>), hipFuncAttributeMaxDynamicSharedMemorySize, LBS_SMEM_MAX);
-  OPTIN(false, false, false) OPTIN(true, false, false) OPTIN(false, true, false) OPTIN(true, true, false) OPTIN(false, true, true) OPTIN(true, true, true)
-#undef OPTIN
-#define OPTINH(DBG_) if (!rc) rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_verts_fwd_kernel<DBG_, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LBS_SMEM_MAX);
-  OPTINH(false) OPTINH(true)
-#undef OPTINH
-  if (!rc) rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(&lbs_verts_fwd_kernel<false, true, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LBS_SMEM_MAX);
-  return rc;
+  static LdsOptinOnce once;
+  return lds_optin(once, {{&lbs_verts_fwd_kernel<false, false, false>, LBS_SMEM_MAX}, {&lbs_verts_fwd_kernel<true, false, false>, LBS_SMEM_MAX},
+                          {&lbs_verts_fwd_kernel<false, true, false>, LBS_SMEM_MAX}, {&lbs_verts_fwd_kernel<true, true, false>, LBS_SMEM_MAX},
+                          {&lbs_verts_fwd_kernel<false, true, true>, LBS_SMEM_MAX}, {&lbs_verts_fwd_kernel<true, true, true>, LBS_SMEM_MAX},
+                          {&lbs_verts_fwd_kernel<false, true, true, true>, LBS_SMEM_MAX}, {&lbs_verts_fwd_kernel<true, true, true, true>, LBS_SMEM_MAX},
+                          {&lbs_verts_fwd_kernel<false, true, true, true, true>, LBS_SMEM_MAX}});
 }
 
 int lbs_verts_fwd(const SkinConst& c, const float* Xg, int Bp, const float* A, int nj, const float* transl,

@@ -11,6 +11,32 @@ using namespace lemo;
 #define S(x) ((hipStream_t)(x))
 #define CHK(e) do { int _e = (e); if (_e) return _e; } while (0)
 
+namespace lemo {
+
+// the only place that sets MaxDynamicSharedMemorySize (kernels.hpp)
+int lds_optin(LdsOptinOnce& once, std::initializer_list<LdsOptin> tab) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LEMO_ERR_ARG;
+  std::call_once(once.flag[dev], [&] {
+    int lds = 0;
+    hipError_t e = hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+    for (const LdsOptin& t : tab)
+      if (e == hipSuccess && t.bytes > lds) e = hipErrorInvalidValue;      // too little LDS: fail here, not at the launch
+    for (const LdsOptin& t : tab)
+      if (e == hipSuccess) e = hipFuncSetAttribute(t.fn, hipFuncAttributeMaxDynamicSharedMemorySize, t.bytes);
+    once.rc[dev] = (int)e;
+  });
+  return once.rc[dev];
+}
+
+int lds_init_all() {
+  for (int (*init)() : {conv_lds_init, conv_split_init, conv_pair_init, conv_wino_init, enc_tail3_init, lbs_init, ae_conv_init})
+    if (int rc = init()) return rc;
+  return 0;
+}
+
+}  // namespace lemo
+
 extern "C" {
 
 int lemo_abi_version(void) { return 5; }
@@ -478,7 +504,7 @@ static int fit_iteration(const lemo_fit_desc& d, hipStream_t s, bool first, bool
 
 void* lemo_fit_create(const lemo_fit_desc* d) {
   if (!d || d->B < (d->per_frame ? 1 : 10) || d->B > d->Bp || !d->verts || !d->transl) return nullptr;
-  if (conv_lds_init() || conv_split_init() || lbs_init()) return nullptr;
+  if (lds_init_all()) return nullptr;
   if (d->pose.XgS && (d->skin.DgH != nullptr) != (d->pose.xgs_f16 != 0)) return nullptr;     // both operands of the blend GEMM in one form
   FitEngine* e = new (std::nothrow) FitEngine();
   if (e) {

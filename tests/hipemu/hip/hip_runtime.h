@@ -29,6 +29,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -67,11 +68,9 @@ typedef void* hipStream_t;
 typedef void* hipGraph_t;
 typedef void* hipGraphExec_t;
 typedef int hipError_t;
-enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorNotSupported = 801 };
+enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorInvalidConfiguration = 9, hipErrorNotSupported = 801 };
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
 enum hipStreamCaptureMode { hipStreamCaptureModeGlobal, hipStreamCaptureModeThreadLocal, hipStreamCaptureModeRelaxed };
-static inline hipError_t hipGetLastError() { return hipSuccess; }
-static inline hipError_t hipPeekAtLastError() { return hipSuccess; }
 static inline const char* hipGetErrorString(hipError_t) { return "hipemu"; }
 static inline hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { memset(p, v, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
@@ -80,7 +79,7 @@ static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline hipError_t hipMalloc(void** p, size_t n) { *p = aligned_alloc(256, (n + 255) / 256 * 256); return *p ? hipSuccess : 2; }
 static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
-static inline hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+enum hipDeviceAttribute_t { hipDeviceAttributeMaxSharedMemoryPerBlock = 74 };
 static inline hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorNotSupported; }
 static inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t*) { return hipErrorNotSupported; }
 static inline hipError_t hipGraphInstantiate(hipGraphExec_t*, hipGraph_t, void*, void*, size_t) { return hipErrorNotSupported; }
@@ -334,7 +333,27 @@ struct Pool {
 };
 inline Pool& pool() { static Pool* p = new Pool(); return *p; }      // leaked on purpose: workers are detached
 
-inline void launch(dim3 grid, dim3 block, size_t shmem, std::function<void()> body) {
+// Devices and the dynamic-LDS opt-in, as on the GPU: the current device is the one hipSetDevice chose on this thread, else
+// HIPEMU_DEVICE (default 0); a launch with more than 64 KiB of dynamic LDS runs only after hipFuncSetAttribute raised that
+// function's limit to at least that much on the current device.  Otherwise it does not run and hipGetLastError reports it.
+inline int& chosen_device() { static thread_local int d = -1; return d; }
+inline int device() {
+  if (chosen_device() >= 0) return chosen_device();
+  const char* e = getenv("HIPEMU_DEVICE");
+  return e ? atoi(e) : 0;
+}
+inline hipError_t& last_error() { static thread_local hipError_t e = hipSuccess; return e; }
+struct Optins { std::mutex m; std::map<std::pair<int, const void*>, size_t> bytes; };      // (device, function) -> bytes
+inline Optins& optins() { static Optins* o = new Optins(); return *o; }
+inline size_t optin_bytes(int dev, const void* fn) {
+  Optins& o = optins();
+  std::lock_guard<std::mutex> lk(o.m);
+  auto it = o.bytes.find({dev, fn});
+  return it == o.bytes.end() ? 0 : it->second;
+}
+
+inline void launch(const void* fn, dim3 grid, dim3 block, size_t shmem, std::function<void()> body) {
+  if (shmem > 65536 && optin_bytes(device(), fn) < shmem) { last_error() = hipErrorInvalidConfiguration; return; }
   Job j;
   j.grid = grid; j.block = block; j.shmem = shmem; j.body = &body;
   j.nblk = (long long)grid.x * grid.y * grid.z;
@@ -358,7 +377,22 @@ inline void launch(dim3 grid, dim3 block, size_t shmem, std::function<void()> bo
 }  // namespace hipemu
 
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-  hipemu::launch((grid), (block), (size_t)(shmem), [=]() { kernel(__VA_ARGS__); })
+  hipemu::launch(reinterpret_cast<const void*>(&kernel), (grid), (block), (size_t)(shmem), [=]() { kernel(__VA_ARGS__); })
+static inline hipError_t hipGetLastError() { const hipError_t e = hipemu::last_error(); hipemu::last_error() = hipSuccess; return e; }
+static inline hipError_t hipPeekAtLastError() { return hipemu::last_error(); }
+static inline hipError_t hipSetDevice(int d) { hipemu::chosen_device() = d; return hipSuccess; }
+static inline hipError_t hipGetDevice(int* d) { *d = hipemu::device(); return hipSuccess; }
+static inline hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) {
+  const char* e = getenv("HIPEMU_MAX_LDS");
+  *v = e ? atoi(e) : 160 * 1024;
+  return hipSuccess;
+}
+static inline hipError_t hipFuncSetAttribute(const void* fn, hipFuncAttribute, int bytes) {
+  hipemu::Optins& o = hipemu::optins();
+  std::lock_guard<std::mutex> lk(o.m);
+  o.bytes[{hipemu::device(), fn}] = (size_t)bytes;
+  return hipSuccess;
+}
 #define LEMO_DYN_SMEM(var) float* var = (float*)hipemu::dyn_smem()
 
 // ---- synchronisation & cross-lane ---------------------------------------------------------
@@ -563,9 +597,6 @@ static inline unsigned atomicMax(unsigned* p, unsigned v) {
 
 // ---- buffer resources / cache-policy loads & stores / scoped atomics (plain memory on the host) ------------
 struct hipDeviceProp_t { int multiProcessorCount; };
-static inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
-enum hipDeviceAttribute_t { hipDeviceAttributeMaxSharedMemoryPerBlock = 74 };
-static inline hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) { *v = 160 * 1024; return hipSuccess; }
 // (workgroups run one after another here: multi-layer chains cannot make progress -- the CPU tests use n = 1)
 static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { p->multiProcessorCount = 1 << 20; return hipSuccess; }
 struct hipemu_rsrc { char* p; };
