@@ -351,6 +351,50 @@ int lemo_ae_conv_f16(const float* in, const float* wt, const float* bias, const 
                      int in_s, int out_s, int cin, int cout, int epi, int mt, int pt, int ks, const float* amax_in, float in_fac,
                      const float* wmax, float* amax_out, void* stream);
 
+/* ---- smoothness-prior training: models/AE_sep.py Enc + Dec (downsample=False, z_channel=64), train_smooth_prior.py:96-136 ----
+ * One step on a batch of network inputs x [bs][H][W] (the reflect-padded velocity image, 245 x 135 for T = 120, 81 markers):
+ *   z = Enc(x), rec = Dec(z), loss = weight_rec * mean|x - rec| + weight_smooth * mean((z[..., 1:] - z[..., :-1])^2),
+ *   torch.optim.Adam(lr) with default betas / eps over all 40 tensors.  fp32 throughout, every sum in a fixed order: two engines
+ *   (and a graph replay and an eager run) give identical bits.  Forward / backward-data of the 32- and 64-channel layers run on
+ *   lemo_conv3x3_mfma_lds, one launch per image and layer; the weight gradients on lemo_wgrad3x3_batched's kernels.
+ *   ws / ws_floats: caller-owned ZEROED device workspace of lemo_sptrain_ws_floats(H, W, bs) floats (0: a shape the kernels do not take:
+ *   2 <= H, 2 <= W <= 139), alive as long as the engine.  use_graph: capture the step once, replay it (same kernels, same bits).
+ * lemo_sptrain_load: flat = lemo_sptrain_n_param() floats (device), the 20 Enc tensors then the 20 Dec tensors in state_dict order
+ *   (enc_blcN.main.{0,2}.{weight,bias}: Conv2d [out][in][3][3]; dec_blcN.deconv{1,2}.{weight,bias}: ConvTranspose2d [in][out][3][3]);
+ *   resets the optimizer.  Step / eval / params / grads before a load: LEMO_ERR_STATE.
+ * lemo_sptrain_step: n steps on x; losses (device, may be NULL) <- {L1 term, smoothness term, weighted total} of the last step.
+ * lemo_sptrain_eval: the same losses under the current parameters, no update; rec (may be NULL) <- [bs][H+2][W+2] (zero border).
+ * lemo_sptrain_params / _grads: the parameters / the last step's gradient in `flat` order. */
+typedef struct lemo_sptrain_desc {
+  int H, W, bs;
+  float lr;
+  float weight_rec, weight_smooth;      /* train_smooth_prior.py defaults: 1.0, 1000.0 */
+  float* ws;
+  long long ws_floats;
+  int use_graph;
+} lemo_sptrain_desc;
+long long lemo_sptrain_ws_floats(int H, int W, int bs);
+int lemo_sptrain_n_param(void);
+void* lemo_sptrain_create(const lemo_sptrain_desc* d);
+void lemo_sptrain_destroy(void* h);
+int lemo_sptrain_load(void* h, const float* flat, void* stream);
+int lemo_sptrain_step(void* h, const float* x, int n, float* losses, void* stream);
+int lemo_sptrain_eval(void* h, const float* x, float* losses, float* rec, void* stream);
+int lemo_sptrain_params(void* h, float* flat_out, void* stream);
+int lemo_sptrain_grads(void* h, float* flat_out, void* stream);
+/* batched 3x3 weight gradient: gw[m][n][ky][kx] = sum_{b,y,x} A_b[m][y][x] B_b[n][y+ky-1][x+kx-1], gb = per-channel sums of B
+ * (bias_b) or A.  ca, cb in {32, 64}: CG8P operands, fp32 MFMA; cb == 1 with ca in {1, 32}: the 1-channel operands are plain padded
+ * images [(H+2)(W+2)], FMA kernel.  Image b's operand starts a_stride / b_stride floats after image b-1's.  ws: device scratch of
+ * lemo_wgrad3x3_batched_ws_floats() floats.  LEMO_ERR_SHAPE for channel counts it does not take or W > 157 (MFMA form). */
+long long lemo_wgrad3x3_batched_ws_floats(int H, int W, int bs, int ca, int cb);
+int lemo_wgrad3x3_batched(const float* A, long long a_stride, const float* B, long long b_stride, int bs, int H, int W, int ca, int cb,
+                          int bias_b, float* ws, float* gw, float* gb, void* stream);
+/* Dec's last block, dec_blc5 (models/AE_sep.py DecBlock_output, stride 1): r1 = lrelu(deconv_{32->1}(u) + b8), rec = deconv_{1->1}(r1)
+ * + b9.  u: 32-channel CG8P per image (u_stride floats apart); w8 [32][1][3][3], w9 [1][1][3][3]; r1, rec: [bs][H+2][W+2], border
+ * left as the caller zeroed it. */
+int lemo_dec_end_fwd(const float* u, long long u_stride, const float* w8, const float* b8, const float* w9, const float* b9, float* r1,
+                     float* rec, int bs, int H, int W, void* stream);
+
 /* ---- stream capture helpers: record everything a host-side step enqueues on `stream` (HIP kernels of this library
  * and the caller's own device work alike) into an executable graph, replay it with one call.  Relaxed capture mode;
  * the caller guarantees that the step does not synchronise and that every buffer it touches outlives the replays. */

@@ -67,6 +67,12 @@ class AeDesc(C.Structure):
     _fields_ = [('H', C.c_int), ('W', C.c_int), ('lr', C.c_float), ('ws', vp), ('ws_floats', C.c_longlong), ('clips', C.c_int)]
 
 
+class SptrainDesc(C.Structure):
+    """lemo_sptrain_desc"""
+    _fields_ = [('H', C.c_int), ('W', C.c_int), ('bs', C.c_int), ('lr', C.c_float), ('weight_rec', C.c_float),
+                ('weight_smooth', C.c_float), ('ws', vp), ('ws_floats', C.c_longlong), ('use_graph', C.c_int)]
+
+
 class SkinConst(C.Structure):
     _fields_ = [('V', C.c_int), ('NC', C.c_int), ('KW', C.c_int), ('blend_fp32', C.c_int)] + \
         [(n, vp) for n in ('Dg', 'v_template', 'w_idx', 'w_val', 'DgH')] + [('dgh_inv', C.c_float)]
@@ -244,6 +250,18 @@ _SIGS = {
     'lemo_ae_wgrad_probe': (C.c_int, [vp, C.c_int, vp]),
     'lemo_ae_conv': (C.c_int, [vp, vp, vp, vp, vp] + [C.c_int] * 12 + [vp]),
     'lemo_ae_conv_f16': (C.c_int, [vp, vp, vp, vp, vp] + [C.c_int] * 12 + [vp, C.c_float, vp, vp, vp]),
+    'lemo_sptrain_ws_floats': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    'lemo_sptrain_n_param': (C.c_int, []),
+    'lemo_sptrain_create': (vp, [C.POINTER(SptrainDesc)]),
+    'lemo_sptrain_destroy': (None, [vp]),
+    'lemo_sptrain_load': (C.c_int, [vp, vp, vp]),
+    'lemo_sptrain_step': (C.c_int, [vp, vp, C.c_int, vp, vp]),
+    'lemo_sptrain_eval': (C.c_int, [vp, vp, vp, vp, vp]),
+    'lemo_sptrain_params': (C.c_int, [vp, vp, vp]),
+    'lemo_sptrain_grads': (C.c_int, [vp, vp, vp]),
+    'lemo_wgrad3x3_batched_ws_floats': (C.c_longlong, [C.c_int] * 5),
+    'lemo_wgrad3x3_batched': (C.c_int, [vp, C.c_longlong, vp, C.c_longlong] + [C.c_int] * 6 + [vp, vp, vp, vp]),
+    'lemo_dec_end_fwd': (C.c_int, [vp, C.c_longlong, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     'lemo_sdf_sample': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]),
     'lemo_fit_create': (vp, [C.POINTER(FitDesc)]),
     'lemo_fit_destroy': (None, [vp]),

@@ -70,6 +70,30 @@ int conv3x3_wino_f16(const float* in, const void* wU, float winv, const float* w
                      int H, int W, int epi, hipStream_t s, unsigned long long* dbg = nullptr);
 int conv3x3_c1(const float* x0, const float* w, const float* bias, float* out, int H, int W, int cout, hipStream_t s);
 int conv3x3_c1_bwd(const float* dpre, const float* w, float* dx0, int H, int W, int cout, hipStream_t s);
+
+// ---------------- prior_train_kernels.hip: the smoothness-prior training step ----------------
+int sp_wgrad_init();
+// out[m][n][ky][kx] = sum_{b,y,x} A_b[m][y][x] B_b[n][y+ky-1][x+kx-1] -> gw; bias sums (of B if bias_b, else of A) -> gb.
+// ca, cb in {32, 64} (fp32 MFMA, CG8P operands) or cb == 1 with ca in {1, 32} (FMA; 1-channel operands are plain padded images)
+int wgrad3x3_batched_ws_floats(int H, int W, int bs, int ca, int cb);
+int wgrad3x3_batched(const float* A, size_t a_stride, const float* B, size_t b_stride, int bs, int H, int W, int ca, int cb,
+                     int bias_b, float* ws, float* gw, float* gb, hipStream_t s);
+// Dec's last block (32 -> 1 + LeakyReLU, 1 -> 1) and the L1 term: x0 / drec / lpart / ctr may be null (forward only)
+int dec_end_lpart_floats(int H, int W, int bs);
+int dec_end_fwd(const float* u, size_t u_stride, const float* w8, const float* b8, const float* w9, const float* b9, float* r1,
+                float* rec, const float* x0, float* drec, float gscale, float* lpart, float* ctr, double lr, int bs, int H, int W,
+                hipStream_t s);
+int dec_end_bwd(const float* drec, const float* w9, const float* r1, float* dpre8, const float* w8, const float* u, size_t u_stride,
+                float* du, int bs, int H, int W, hipStream_t s);
+struct SpPackJob { float* wt; float* wt2; int src, cin, cout, trans, first; };
+#define SP_MAX_PACK 40
+struct SpPackJobs { SpPackJob j[SP_MAX_PACK]; int n, total; };
+int sp_repack(const SpPackJobs& J, const float* theta, hipStream_t s);
+int sp_pad(const float* x, float* x0, int bs, int H, int W, hipStream_t s);
+int sp_add(float* dst, const float* src, size_t n, hipStream_t s);
+int sp_losses(const float* lpart, int nl, const float* spart, int ns, double n_rec, double n_smooth, float w_rec, float w_smooth,
+              float* losses, hipStream_t s);
+int sp_adam(float* theta, float* m, float* v, const float* g, const float* ctr, int n, hipStream_t s);
 int smooth_loss_blocks(int H, int W, int C);
 int smooth_loss(const float* z, float* dpre, float* partial, int H, int W, int C, float coef2, hipStream_t s,
                 double* acc = nullptr);

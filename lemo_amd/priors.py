@@ -397,3 +397,88 @@ def warn_if_wide_image(lib, H: int, W: int, conv_variant: int) -> bool:
                       RuntimeWarning, stacklevel=3)
         return True
     return False
+
+
+# ----------------------------------------------------------------------------------------------
+# Decoder of the smoothness prior
+# ----------------------------------------------------------------------------------------------
+
+DEC_IN = [64, 64, 64, 64, 64, 64, 64, 32, 32, 1]
+DEC_OUT = [64, 64, 64, 64, 64, 64, 32, 32, 1, 1]
+"""models/AE_sep.py:102-122 with downsample=False, z_channel=64: (nin, nout) of the 10 stride-1 transposed convolutions."""
+
+
+def dec_layer_keys() -> List[str]:
+    return [f'dec_blc{b}.deconv{i}' for b in range(1, 6) for i in (1, 2)]
+
+
+class _DeconvParam(nn.Module):
+    """ConvTranspose2d weight [nin][nout][3][3] / bias under the reference's `deconvN` key names"""
+
+    def __init__(self, nin, nout):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(nin, nout, 3, 3))
+        self.bias = nn.Parameter(torch.zeros(nout))
+
+
+class _DecBlockParams(nn.Module):
+    def __init__(self, nin, nout):
+        super().__init__()
+        self.deconv1 = _DeconvParam(nin, nout)
+        self.deconv2 = _DeconvParam(nout, nout)
+
+
+class Dec(nn.Module):
+    """Drop-in for ``models/AE_sep.py::Dec(downsample=False, z_channel=64)``: same ``state_dict`` keys
+    (``dec_blcN.deconv{1,2}.{weight,bias}``), ``forward(z, input_size, s1, s2, s3, s4) -> rec [bs, 1, H, W]``.  At stride 1 a
+    ConvTranspose2d is the 3x3 convolution with the transposed, flipped weights (:func:`pack_conv3x3_bwd`): the first 8 layers run
+    on lemo_conv3x3_mfma_lds, dec_blc5 on lemo_dec_end_fwd.  Inference only (training: lemo_amd.smooth_train)."""
+
+    def __init__(self, downsample=False, z_channel=64, _lib=None):
+        super().__init__()
+        if downsample or z_channel != 64:
+            raise NotImplementedError('LEMO instantiates the smoothness decoder as Dec(downsample=False, z_channel=64)')
+        for b in range(1, 6):
+            setattr(self, f'dec_blc{b}', _DecBlockParams(DEC_IN[2 * b - 2], DEC_OUT[2 * b - 2]))
+        self._lib_override, self._cache = _lib, {}
+
+    def packed(self, device):
+        ps = list(self.parameters())
+        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in ps)
+        if self._cache.get('key') != key:
+            sd = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in self.state_dict().items()}
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(device)
+            wt, wt2, bias = [], [], []
+            for j, k in enumerate(dec_layer_keys()):
+                w = sd[k + '.weight']
+                assert w.shape == (DEC_IN[j], DEC_OUT[j], 3, 3), (k, w.shape)
+                if j < 8:
+                    wt.append(t(pack_conv3x3_bwd(w))); wt2.append(t(pack_conv3x3_bwd_gmajor(w)))
+                else:
+                    wt.append(t(w.reshape(DEC_IN[j], 9))); wt2.append(None)
+                bias.append(t(sd[k + '.bias']))
+            self._cache = dict(key=key, packs=(wt, wt2, bias))
+        return self._cache['packs']
+
+    def forward(self, z, input_size=None, s1=None, s2=None, s3=None, s4=None):
+        assert z.dim() == 4 and z.shape[1] == 64, 'z: [bs, 64, H, W]'
+        lib = self._lib_override or _hip.get_lib()
+        z = z.detach().contiguous().float()
+        _hip.check_device(lib, z)
+        bs, _, H, W = z.shape
+        dev = z.device
+        s = lib.stream(dev)
+        wt, wt2, bias = self.packed(dev)
+        cur = [to_cg8p(z[b]) for b in range(bs)]
+        for j in range(8):
+            nxt = [cg8p_alloc(64, H, W, dev) for _ in range(bs)]
+            for b in range(bs):
+                lib.check(lib.conv3x3_mfma_lds(ptr(cur[b]), ptr(wt[j]), ptr(wt2[j]), ptr(bias[j]), None, ptr(nxt[b]), H, W,
+                                               DEC_IN[j], DEC_OUT[j], 0, s), 'conv3x3_mfma_lds')
+            cur = nxt
+        u = torch.stack(cur)                                   # [bs][8][(H+2)(W+2)][8] (32 channels used)
+        r1 = torch.zeros(bs, H + 2, W + 2, dtype=torch.float32, device=dev)
+        rec = torch.zeros_like(r1)
+        lib.check(lib.dec_end_fwd(ptr(u), u[0].numel(), ptr(wt[8]), ptr(bias[8]), ptr(wt[9]), ptr(bias[9]), ptr(r1), ptr(rec),
+                                  bs, H, W, s), 'dec_end_fwd')
+        return rec[:, 1:-1, 1:-1].unsqueeze(1).contiguous()
