@@ -86,6 +86,20 @@ int lemo_conv3x3_pair_supported(int H, int W, int c0, int c1, int c2);
 int lemo_conv3x3_pair_f16(const float* in, const void* wA, float winvA, const float* biasA, const float* auxA, float* mid,
                           const void* wB, float winvB, const float* biasB, const float* auxB, float* out, int H, int W, int epi,
                           unsigned long long* dbg, void* stream);
+/* The encoder's turn (conv variant 9's step schedule, csrc/conv_turn_kernels.hip): layer 9 forward, the latent smoothness loss
+ * gradient and layer 9 backward-data in ONE launch, on 12 x 12 output tiles with everything between the two convolutions in LDS:
+ *   z = lrelu(conv(in, wf) + bias) (the owned pixels written to z, CG8P 64 channels: act[10]);
+ *   d(pre-act 10) = coef2 * 2-sided time difference of z * lrelu'(z), zero outside the image (lemo_smooth_loss's arithmetic: for
+ *     equal z the values are bit-identical);
+ *   out = conv^T(d(pre-act 10), wb) * lrelu'(in) (d(pre-act 9)).
+ * wf / wb: pack_conv3x3_split_f16 / pack_conv3x3_bwd_split_f16 of layer 9, winvf / winvb their inverse host scales.  acc (may be
+ * NULL): f64 [32][16]; every workgroup adds its sum of (z[x+1] - z[x])^2 over its owned pixels and channels to acc[(wg & 31) * 16].
+ * dpre (may be NULL): receives d(pre-act 10) of every image pixel (CG8P).  dbg (may be NULL): per wave {HW_ID, start, after staging,
+ * after layer 9 forward, after the stencil, after the dpre planes, end} stamps; ceil(H / 12) * ceil(W / 12) workgroups x 8 waves x 8.
+ * Refuses W < 2 (no time difference). */
+int lemo_conv3x3_turn_supported(int H, int W);
+int lemo_conv3x3_turn_f16(const float* in, const void* wf, float winvf, const float* bias, const void* wb, float winvb, float* z, float* out,
+                          double* acc, float coef2, int H, int W, float* dpre, unsigned long long* dbg, void* stream);
 /* variant 10 (round 6): ONE 64 -> 64 layer (forward, epi 0, models/AE_sep.py:11-30; backward-data, epi 1) as a Winograd F(2x2, 3x3)
  * convolution: 16 instead of 36 multiplies per 2 x 2 output tile and (cin, cout), the 16 [64 x 64 x tiles] GEMMs in the split-f16
  * arithmetic of variant 4 (fp32 transforms, two fp16 pieces per operand, 3 MFMA products, fp32 accumulate).  A workgroup owns 32
@@ -442,7 +456,9 @@ typedef struct lemo_fit_desc {
   int conv_variant;               /* kernel family of the encoder's MFMA layers (the struct has no default: 0 selects lemo_conv3x3_mfma variant 0;
                                    * lemo_amd.priors.DEFAULT_CONV_VARIANT = 9 is what the Python fitters pass and what every gate runs on):
                                    * 9 (shipped): lemo_enc_head3 (image + layers 0-2) + fused 64 -> 64 pairs (lemo_conv3x3_pair_f16) + lemo_enc_tail3
-                                   *    (layers 2-0 backwards), split-f16 arithmetic throughout ; 8: 9 with layer 2's backward a launch of its own ;
+                                   *    (layers 2-0 backwards), split-f16 arithmetic throughout; lemo_fit_step runs layer 9, the smoothness loss and
+                                   *    layer 9's backward as ONE launch (lemo_conv3x3_turn_f16; the environment variable LEMO_ENC_TURN=0, read by
+                                   *    lemo_fit_create, keeps the three launches) ; 8: 9 with layer 2's backward a launch of its own ;
                                    * 7: head / tail without layer 2 (lemo_enc_head / lemo_enc_tail) ; 5: pairs only, head and tail layer by layer ;
                                    * 10 (round 6): 9 with every 64 -> 64 layer ONE Winograd launch (lemo_conv3x3_wino_f16) instead of the pairs --
                                    *    parity-green, measured slower, enc_w3 / enc_wbwd3 of those layers then hold the Winograd packs ;

@@ -54,11 +54,12 @@ static inline int enc_layer(const D& d, int l, bool bwd, const float* src, float
 // layers 1..9 forward: act[1] -> act[10].  conv_variant >= 5: consecutive layers whose three channel counts the pair kernel takes
 // run as ONE launch (64 -> 64 -> 64: layers (3,4), (5,6), (7,8); 6 launches instead of 9), the intermediate activation is still
 // written (the backward pass reads every act[l])
+// l_end = 9: stop before layer 9 (the turn launch runs it: enc_turn below)
 template <class D>
-static inline int enc_chain_fwd(const D& d, int H, int W, hipStream_t s, int l_first = 1) {
+static inline int enc_chain_fwd(const D& d, int H, int W, hipStream_t s, int l_first = 1, int l_end = 10) {
   int l = l_first;                 // (2 when enc_head produced act[2] already: conv variant 7)
-  while (l < 10) {
-    if (d.conv_variant >= 5 && d.conv_variant != 10 && l + 1 < 10 && d.enc_w3[l] && d.enc_w3[l + 1] &&
+  while (l < l_end) {
+    if (d.conv_variant >= 5 && d.conv_variant != 10 && l + 1 < l_end && d.enc_w3[l] && d.enc_w3[l + 1] &&
         conv3x3_pair_supported(H, W, d.enc_ch[l], d.enc_ch[l + 1], d.enc_ch[l + 2])) {
       ENC_CHK(conv3x3_pair_f16(d.act[l], d.enc_w3[l], d.enc_w3_inv[l], d.enc_b[l], nullptr, d.act[l + 1],
                                                                            d.enc_w3[l + 1], d.enc_w3_inv[l + 1], d.enc_b[l + 1], nullptr, d.act[l + 2],
@@ -74,9 +75,10 @@ static inline int enc_chain_fwd(const D& d, int H, int W, hipStream_t s, int l_f
 
 // layers 9..1 backward-data: d(pre-act 10) in dact[0] -> d(pre-act 1) in dact[*cur_out] through the two ping-pong maps.
 // conv_variant >= 5: pairs (9,8), (7,6), (5,4) in one launch each -- the intermediate gradient map never leaves the CU
+// l_first = 8: d(pre-act 9) in dact[0] (the turn launch ran layer 9's backward-data); the pairs are then (8,7), (6,5), (4,3)
 template <class D>
-static inline int enc_chain_bwd(const D& d, int H, int W, hipStream_t s, int* cur_out, int l_last = 1) {
-  int cur = 0, l = 9;              // (l_last = 2: enc_tail takes d(pre-act 2) from here: conv variant 7)
+static inline int enc_chain_bwd(const D& d, int H, int W, hipStream_t s, int* cur_out, int l_last = 1, int l_first = 9) {
+  int cur = 0, l = l_first;        // (l_last = 2: enc_tail takes d(pre-act 2) from here: conv variant 7)
   while (l >= l_last) {
     if (d.conv_variant >= 5 && d.conv_variant != 10 && l - 1 >= l_last && d.enc_wbwd3[l] && d.enc_wbwd3[l - 1] &&
         conv3x3_pair_supported(H, W, d.enc_ch[l + 1], d.enc_ch[l], d.enc_ch[l - 1])) {
@@ -92,6 +94,16 @@ static inline int enc_chain_bwd(const D& d, int H, int W, hipStream_t s, int* cu
   }
   *cur_out = cur;
   return 0;
+}
+
+// conv variant 9's step schedule (lemo_fit_step; LEMO_ENC_TURN=0 keeps the chain above): layer 9 forward, the smoothness loss gradient
+// and layer 9 backward-data as ONE launch (conv_turn_kernels.hip) between the forward pairs (3,4) (5,6) (7,8) and the backward pairs
+// (8,7) (6,5) (4,3).  Only where every 64 -> 64 layer of the chain pairs up the same way.
+template <class D> static inline bool enc_turn_usable(const D& d, int H, int W) {
+  if (d.conv_variant != 9 || !enc_fused_head3(d) || !enc_fused_tail3(d) || !conv3x3_turn_supported(H, W)) return false;
+  for (int l = 3; l <= 9; ++l)
+    if (d.enc_ch[l] != 64 || !d.enc_w3[l] || !d.enc_wbwd3[l]) return false;
+  return d.enc_ch[10] == 64 && d.enc_b[9] && conv3x3_pair_supported(H, W, 64, 64, 64);
 }
 
 }  // namespace lemo

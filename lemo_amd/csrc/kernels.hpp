@@ -29,6 +29,7 @@ int lds_init_all();
 int conv_lds_init();
 int conv_split_init();
 int conv_pair_init();
+int conv_turn_init();
 int conv_wino_init();
 int enc_tail3_init();
 int lbs_init();
@@ -62,6 +63,20 @@ int conv3x3_mfma_split(const float* in, const void* w3, const float* wt, const f
 bool conv3x3_pair_supported(int H, int W, int c0, int c1, int c2);
 int conv3x3_pair_f16(const float* in, const void* wA, float winvA, const float* biasA, const float* auxA, float* mid, const void* wB,
                      float winvB, const float* biasB, const float* auxB, float* out, int H, int W, int epi, hipStream_t s,
+                     unsigned long long* dbg = nullptr);
+// ---------------- conv_turn_kernels.hip ----------------
+// the per-frame losses (vertex_loss_body's terms) as extra workgroups of the turn launch
+struct FrameLoss {
+  lemo_fit_const fc;
+  const float *verts, *target, *contact, *shape, *other;
+  int nrows, B;
+  double* acc;                     // f64 [32 slots][16] (the fit engine's loss_acc)
+};
+// conv variant 9's step schedule: layer 9 forward -> smoothness loss gradient -> layer 9 backward-data in ONE launch (12 x 12 tiles)
+bool conv3x3_turn_supported(int H, int W);
+int conv3x3_turn_tiles(int H, int W);
+int conv3x3_turn_f16(const float* in, const void* wf, float winvf, const float* bias, const void* wb, float winvb, float* z, float* out,
+                     double* acc, float coef2, int H, int W, float* dpre, const FrameLoss* fl, hipStream_t s,
                      unsigned long long* dbg = nullptr);
 // ---------------- conv_wino_kernels.hip ----------------
 // variant 10: ONE 64 -> 64 layer as a Winograd F(2x2, 3x3) convolution, its 16 GEMMs in the split-f16 arithmetic of variant 4

@@ -30,7 +30,7 @@ int lds_optin(LdsOptinOnce& once, std::initializer_list<LdsOptin> tab) {
 }
 
 int lds_init_all() {
-  for (int (*init)() : {conv_lds_init, conv_split_init, conv_pair_init, conv_wino_init, enc_tail3_init, lbs_init, ae_conv_init, sp_wgrad_init})
+  for (int (*init)() : {conv_lds_init, conv_split_init, conv_pair_init, conv_turn_init, conv_wino_init, enc_tail3_init, lbs_init, ae_conv_init, sp_wgrad_init})
     if (int rc = init()) return rc;
   return 0;
 }
@@ -89,6 +89,11 @@ int lemo_conv3x3_pair_f16(const float* in, const void* wA, float winvA, const fl
                           const void* wB, float winvB, const float* biasB, const float* auxB, float* out, int H, int W, int epi,
                           unsigned long long* dbg, void* stream) {
   return conv3x3_pair_f16(in, wA, winvA, biasA, auxA, mid, wB, winvB, biasB, auxB, out, H, W, epi, S(stream), dbg);
+}
+int lemo_conv3x3_turn_supported(int H, int W) { return conv3x3_turn_supported(H, W) ? 1 : 0; }
+int lemo_conv3x3_turn_f16(const float* in, const void* wf, float winvf, const float* bias, const void* wb, float winvb, float* z, float* out,
+                          double* acc, float coef2, int H, int W, float* dpre, unsigned long long* dbg, void* stream) {
+  return conv3x3_turn_f16(in, wf, winvf, bias, wb, winvb, z, out, acc, coef2, H, W, dpre, nullptr, S(stream), dbg);
 }
 int lemo_enc_head(const lemo_fit_const* fc, const float* verts, int nrows, const float* Jtr, int nj, const float* transl, int B, const float* w0,
                   const float* b0, const void* w1pack, float w1inv, const float* b1, float* x0, float* canon, float* act1, float* act2,
@@ -304,15 +309,16 @@ struct FitEngine {
   hipGraphExec_t exec[FIT_MAXG + 1] = {};      // exec[k] = k iterations
   int head = 5;     // > 0: a call opens with a 1-iteration and a `head`-iteration graph (LEMO_FIT_HEAD overrides; 0 = largest graphs first)
   FitSide fs;       // side stream + events of the all-vertex side launch (lemo_fit_desc.verts_side); unused otherwise
+  bool turn = true; // step schedule of conv variant 9: the turn launch (enc_turn_usable); LEMO_ENC_TURN=0 keeps the split + fit_losses chain
 };
 
-static int fit_iteration(const lemo_fit_desc& d, hipStream_t s, bool first, bool last, FitSide* fs);
+static int fit_iteration(const lemo_fit_desc& d, hipStream_t s, bool first, bool last, FitSide* fs, bool turn);
 
 static int capture_iterations(FitEngine* e, hipStream_t s, int iters, hipGraphExec_t* out) {
   hipGraph_t g = nullptr;
   CHK((int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   int rc = 0;
-  for (int i = 0; i < iters && !rc; ++i) rc = fit_iteration(e->d, s, i == 0, i == iters - 1, &e->fs);
+  for (int i = 0; i < iters && !rc; ++i) rc = fit_iteration(e->d, s, i == 0, i == iters - 1, &e->fs, e->turn);
   const int ec = (int)hipStreamEndCapture(s, &g);
   if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
   CHK(ec);
@@ -394,9 +400,15 @@ static int fit_side_join(FitSide* fs, hipStream_t s) {
 // a run of iterations the previous iteration's tail launch has already produced it from the updated latent
 // `stages` (diagnostics, lemo_fit_census): bit 0 VPoser + pose stage, 1 vertex stage, 2 marker image + encoder forward, 3 losses
 // fs: the side-branch context of a run of iterations (null: a bare forward -- the all-vertex forward of verts_side then runs in line)
-static int fit_forward(const lemo_fit_desc& d, hipStream_t s, bool finalize, bool compute_h1 = true, unsigned stages = ~0u, FitSide* fs = nullptr) {
+// turn: the step schedule of conv variant 9 where enc_turn_usable (enc_chain.hpp): the forward stops at act[9] and the `losses` stage is
+// the turn launch (layer 9 forward -> act[10], smoothness loss + gradient, layer 9 backward-data -> d(pre-act 9) in dact[0], and the
+// per-frame losses as extra workgroups) -- fit_backward must then be called with the same flag.  A bare forward (lemo_fit_forward)
+// keeps layer 9 + fit_losses: it reports the losses without running any backward.
+static int fit_forward(const lemo_fit_desc& d, hipStream_t s, bool finalize, bool compute_h1 = true, unsigned stages = ~0u, FitSide* fs = nullptr,
+                       bool turn = false) {
   const int B = d.B, nj = d.body.nj;
   const int H = 3 * d.fit.n81 + 2, W = B - 1 + 16;
+  const bool tn = turn && !d.per_frame && enc_turn_usable(d, H, W);
   // VPoser MLP (3 MFMA GEMMs); its rotation head and the 6-D -> axis-angle conversion of the global
   // orientation are fused into the pose-stage kernel, which also zeroes the loss accumulators and
   // latches the step counter for this iteration.
@@ -438,11 +450,15 @@ static int fit_forward(const lemo_fit_desc& d, hipStream_t s, bool finalize, boo
                  d.act[1], d.act[2], s));
   else
     CHK(marker_c1(d.fit, d.verts, d.nrows, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.x0, d.canon, d.act[1], d.enc_ch[1], s));
-  CHK(enc_chain_fwd(d, H, W, s, enc_fused_head3(d) ? 3 : (enc_fused_head(d) ? 2 : 1)));
+  CHK(enc_chain_fwd(d, H, W, s, enc_fused_head3(d) ? 3 : (enc_fused_head(d) ? 2 : 1), tn ? 9 : 10));
   }
   const double cnt = (double)d.enc_ch[10] * H * (W - 1);
   const float coef2 = (float)((double)d.weights_host[5] * 2.0 / cnt);
-  if (stages & 8u)
+  if ((stages & 8u) && tn) {
+    const FrameLoss fl{d.fit, d.verts, d.target, d.contact, d.shape, d.other, d.nrows, B, d.loss_acc};
+    CHK(conv3x3_turn_f16(d.act[9], d.enc_w3[9], d.enc_w3_inv[9], d.enc_b[9], d.enc_wbwd3[9], d.enc_wbwd3_inv[9], d.act[10], d.dact[0],
+                         d.loss_acc + 9, coef2, H, W, nullptr, &fl, s));
+  } else if (stages & 8u)
   CHK(fit_losses(d.act[10], d.dact[0], H, W, d.enc_ch[10], coef2, d.loss_acc + 9, d.fit, d.verts, d.nrows, d.target, d.contact,
                  d.shape, d.other, B, d.loss_acc, s));
   if (finalize) CHK(loss_finalize(d.loss_acc, B, d.fit.n67, cnt, d.weights, d.losses, s));
@@ -452,13 +468,25 @@ static int fit_forward(const lemo_fit_desc& d, hipStream_t s, bool finalize, boo
 // update = false: gradients only (lemo_fit_backward).  update = true: the tail launch also runs Adam and, with next_h1,
 // the first VPoser layer of the next iteration.
 // `stages`: bit 4 encoder backward-data + first-layer adjoint, 5 vertex-stage backward, 6 pose / VPoser backward + tail
-static int fit_backward(const lemo_fit_desc& d, hipStream_t s, bool update = false, bool next_h1 = false, unsigned stages = ~0u, FitSide* fs = nullptr) {
+// turn: continue from the forward's turn launch (d(pre-act 9) in dact[0]).  turn_here (lemo_fit_backward after lemo_fit_forward, whose
+// forward kept layer 9 + fit_losses): run the turn launch first, without loss accumulation or frame roles (the losses are the forward's)
+// and with z going to dact[1] (scratch until the first backward pair writes it; act[10] keeps the forward's z), so that the gradient is
+// bit for bit the one lemo_fit_step computes from the same state.
+static int fit_backward(const lemo_fit_desc& d, hipStream_t s, bool update = false, bool next_h1 = false, unsigned stages = ~0u, FitSide* fs = nullptr,
+                        bool turn = false, bool turn_here = false) {
   const int B = d.B, nj = d.body.nj;
   const int H = 3 * d.fit.n81 + 2, W = B - 1 + 16;
+  const bool tn = turn && !d.per_frame && enc_turn_usable(d, H, W);
   const double cnt = d.per_frame ? 1.0 : (double)d.enc_ch[10] * H * (W - 1);
   int cur = 0;
   if (d.per_frame || !(stages & 16u)) goto vertex_stage;           // per_frame: no encoder (d.fit.u_m81 is all -1, dx0 is never read)
-  CHK(enc_chain_bwd(d, H, W, s, &cur, enc_bwd_l_last(d)));          // d(pre-act of layer 10) -> ... -> d(pre-act of layer 1)
+  if (tn && turn_here) {
+    const double cnt10 = (double)d.enc_ch[10] * H * (W - 1);
+    const float coef2 = (float)((double)d.weights_host[5] * 2.0 / cnt10);
+    CHK(conv3x3_turn_f16(d.act[9], d.enc_w3[9], d.enc_w3_inv[9], d.enc_b[9], d.enc_wbwd3[9], d.enc_wbwd3_inv[9], d.dact[1], d.dact[0],
+                         nullptr, coef2, H, W, nullptr, nullptr, s));
+  }
+  CHK(enc_chain_bwd(d, H, W, s, &cur, enc_bwd_l_last(d), tn ? 8 : 9));   // d(pre-act of layer 10 | 9 after the turn) -> ... -> d(pre-act 1)
   CHK(enc_bwd_tail(d, cur, H, W, s));
   if (fs && d.verts_side && !d.full_vertices) {            // fork: the all-vertex forward beside the per-frame launches below
     if (fs->side) {
@@ -493,11 +521,11 @@ pose_stage:
 }
 
 // first / last: position inside the run of iterations issued together (one graph, or one eager call)
-static int fit_iteration(const lemo_fit_desc& d, hipStream_t s, bool first, bool last, FitSide* fs) {
+static int fit_iteration(const lemo_fit_desc& d, hipStream_t s, bool first, bool last, FitSide* fs, bool turn) {
   const bool side = d.verts_side && !d.full_vertices && !d.per_frame;
-  CHK(fit_forward(d, s, false, first, ~0u, side ? fs : nullptr));
+  CHK(fit_forward(d, s, false, first, ~0u, side ? fs : nullptr, turn));
   if (side && !fs) return LEMO_ERR_STATE;
-  CHK(fit_backward(d, s, true, !last, ~0u, side ? fs : nullptr));
+  CHK(fit_backward(d, s, true, !last, ~0u, side ? fs : nullptr, turn));
   if (last) CHK(fit_side_join(fs, s));                     // a run / a captured graph ends with everything on the caller's stream
   return 0;
 }
@@ -514,6 +542,7 @@ void* lemo_fit_create(const lemo_fit_desc* d) {
     // and the host thread is what limits several clips in lockstep (tools/perframe_concurrent.py)
     if (d->per_frame) e->head = 0;
     if (const char* h = getenv("LEMO_FIT_HEAD")) e->head = atoi(h);       // diagnostics: A/B of the replay schedule
+    if (const char* t = getenv("LEMO_ENC_TURN")) e->turn = atoi(t) != 0;   // A/B of the encoder's step schedule (conv variant 9)
     if (d->verts_side && !d->full_vertices) {
       if (!d->transl_side || d->per_frame) { delete e; return nullptr; }
       // (the host emulation hands back a null stream: FitSide::side == nullptr = "no second stream", the launch then runs in line)
@@ -545,7 +574,7 @@ int lemo_fit_forward(void* h, void* stream) {
 int lemo_fit_backward(void* h, void* stream) {       // after lemo_fit_forward: gradients only, no Adam
   FitEngine* e = (FitEngine*)h;
   if (!e) return LEMO_ERR_ARG;
-  return fit_backward(e->d, S(stream));
+  return fit_backward(e->d, S(stream), false, false, ~0u, nullptr, e->turn, true);
 }
 
 int lemo_fit_step(void* h, int n, int use_graph, void* stream) {
@@ -553,7 +582,7 @@ int lemo_fit_step(void* h, int n, int use_graph, void* stream) {
   if (!e || n < 0) return LEMO_ERR_ARG;
   hipStream_t s = S(stream);
   if (!use_graph) {
-    for (int i = 0; i < n; ++i) CHK(fit_iteration(e->d, s, i == 0, i == n - 1, &e->fs));
+    for (int i = 0; i < n; ++i) CHK(fit_iteration(e->d, s, i == 0, i == n - 1, &e->fs, e->turn));
     return 0;
   }
   CHK(fit_graphs(e, s, n, false));
@@ -586,8 +615,8 @@ int lemo_fit_census(void* h, int reps, float* ms_out, void* stream) {
     hipGraphExec_t x = nullptr;
     rc = (int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
     for (int r = 0; r < reps && !rc; ++r) {
-      if (mask & 15u) rc = fit_forward(d, s, false, true, mask);
-      if (!rc && (mask & 112u)) rc = fit_backward(d, s, false, false, mask);
+      if (mask & 15u) rc = fit_forward(d, s, false, true, mask, nullptr, e->turn);
+      if (!rc && (mask & 112u)) rc = fit_backward(d, s, false, false, mask, nullptr, e->turn);
     }
     const int ec = (int)hipStreamEndCapture(s, &g);
     if (!rc) rc = ec;

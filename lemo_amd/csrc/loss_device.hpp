@@ -151,6 +151,70 @@ __device__ __forceinline__ void vertex_loss_body(int b, FitConst fc, const float
   }
 }
 
+// vertex_loss_body for ONE frame on the 16 lanes of a DPP row (the frame roles of the encoder's turn launch, conv_turn_kernels.hip:
+// 32 frames per 512-thread workgroup instead of one 256-thread workgroup per frame).  Same terms and accumulator slots; the per-frame
+// sums are taken in another order (16 lanes, row16_sum), which moves them by fp32 rounding only.  Every gather of a term is issued
+// before the first use (clamped indices, switched by selects).  All 64 lanes of the wave must reach it; b >= B contributes nothing.
+__device__ __forceinline__ void vertex_loss_row16(int b, int l, const FrameLoss& fl) {
+  const FitConst& fc = fl.fc;
+  const bool valid = b < fl.B;
+  const int bb = valid ? b : fl.B - 1;
+  float acc[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) acc[i] = 0.f;
+  const int n = fc.n67 * 3;
+  for (int w0 = 0; w0 < n; w0 += 16 * 8) {
+    int rowv[8];
+    float tv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int w = min(w0 + u * 16 + l, n - 1), m = w / 3;
+      rowv[u] = fc.row67[m];
+      tv[u] = fl.target[((size_t)bb * fc.n67 + m) * 3 + (w - 3 * m)];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int w = w0 + u * 16 + l, wc = min(w, n - 1);
+      const float v = fl.verts[((size_t)bb * fl.nrows + rowv[u]) * 3 + (wc - 3 * (wc / 3))];
+      acc[0] += w < n ? fabsf(v - tv[u]) : 0.f;
+    }
+  }
+  if (bb < fl.B - 1) {
+    float ct[4];
+    int fs[5];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ct[k] = fl.contact[(size_t)bb * 4 + k];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) fs[k] = fc.foot_start[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (ct[k] != 1.f) continue;
+      for (int q = fs[k] + l; q < fs[k + 1]; q += 16) {
+        const float* v0 = fl.verts + ((size_t)bb * fl.nrows + fc.foot_row[q]) * 3;
+        const float* v1 = v0 + (size_t)fl.nrows * 3;
+        const float vx = (v1[0] - v0[0]) * 30.f, vy = (v1[1] - v0[1]) * 30.f, vz = (v1[2] - v0[2]) * 30.f;
+        const float sp = sqrtf(vx * vx + vy * vy + vz * vz);
+        if (sp - 0.1f > 0.f) { acc[1 + k] += sp; acc[5 + k] += 1.f; }
+      }
+    }
+  }
+  {                                // L2 priors: z (32), betas (10), hands (24)
+    const float* o = fl.other + (size_t)bb * 56;
+    const float z0 = o[l], z1 = o[16 + l], h0 = o[32 + l], h1 = o[32 + 16 + (l & 7)];
+    const float be = fl.shape[(size_t)bb * 10 + (l < 10 ? l : 0)];
+    acc[9] = z0 * z0 + z1 * z1;
+    acc[10] = l < 10 ? be * be : 0.f;
+    acc[11] = h0 * h0 + (l < 8 ? h1 * h1 : 0.f);
+  }
+#pragma unroll
+  for (int i = 0; i < 12; ++i) acc[i] = row16_sum(valid ? acc[i] : 0.f);
+  if (valid && l == 0) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i)
+      if (acc[i] != 0.f) atomicAdd(fl.acc + (b & 31) * 16 + (i < 9 ? i : i + 1), (double)acc[i]);
+  }
+}
+
 // ---- d(total)/d(verts) pieces (opt_amass_temp.py:359-425 differentiated by hand) --------------------------------
 // losses[0..6] = marker, vposer, shape, hand, contact, smooth, total ; losses[8..11] = 1/count per foot set
 // weights[0..5] = rec_markers, vposer, shape, hand, contact_vel, smooth   (opt_amass_temp.py:47-52)
