@@ -4,15 +4,21 @@ opt_amass_temp.py, one 4 s / 30 fps clip = B 119 frames, smoothness + contact + 
 losses, Adam), one independent sequence per GPU.
 
     python bench.py --gpus 1 --steps 100 --warmup 10
+    python bench.py --gpus 1 --steps 100 --warmup 10 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is ONE full Adam iteration (forward incl. all 10475 vertices/frame, backward, update).
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run does only what the headline figure needs: it
+sets up, ramps and warms up, times the K steps, writes ``--dump-outputs`` and prints the line.  ``--full`` then measures, on
+the same engine, everything else the line can carry (:func:`full_measurements`: a second 100-step window, the stage census,
+concurrent clips, the kernel-family A/B, MPJPE against the oracle, the coherent model; then the other workloads of
+BASELINE.json), among them two objects:
   roofline     -- dominant kernel (64->64 3x3 conv, fp32-exact operands on the bf16 matrix cores): algorithmic FLOP /
                   launch duration measured live with HIP events on the engine's stream; ``roofline.hbm`` = the same
                   for the vertex stage (lbs_verts_fwd, HBM-bound side, SURVEY 8(d) "report both")
   cpu_baseline -- the oracle (faithful restatement, two SMPL-X forwards like the reference) timed on
                   this node's host cores on a bounded sample (N=1, rank 0 only).
+``--no-extras``, ``--no-cpu-baseline`` and ``--concurrent-clips 0`` leave parts of ``--full`` out.
 Before the W warm-up steps the graphs of the run are captured and uploaded and the device is brought to its steady
 state: the iteration graph is replayed for ``--ramp-ms`` (measured, tools/overhead_probe.py: the same 20-step call
 takes 7.9 ms on an idle device and 7.27 ms after ~200 iterations -- DVFS follows the sustained load of the real kernel
@@ -670,7 +676,7 @@ def main_prox(args, world, rank, device):
         print(json.dumps(out), flush=True)
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
@@ -683,23 +689,31 @@ def main():
                     help='synthetic SMPL-X-shaped model: skinning joints i.i.d. per vertex (the worst case, rounds 1-3) or with the index '
                          'locality of the licensed model (lemo_amd.synthetic._coherent_skinning)')
     ap.add_argument('--conv-variant', type=int, default=DEFAULT_CONV_VARIANT)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline line\'s own work, also measure everything else the line can carry: a second 100-step window, '
+                         'the stage census, the roofline, concurrent clips, the kernel-family A/B, MPJPE vs the oracle, the coherent model, the '
+                         'other workloads and the CPU baseline (off by default: a plain run sets up, warms up, times and prints)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--ramp-ms', type=float, default=250.0, help='untimed replay of the iteration before the warm-up steps (0 = off)')
     ap.add_argument('--workload', choices=('amass', 'prox'), default='amass',
                     help="amass (default, the headline: BASELINE configs[1]/[2]) or prox (configs[4]'s per-GPU leg: one S3 window per GPU)")
-    ap.add_argument('--no-extras', action='store_true', help='skip the non-headline objects (prox_window, perframe, ae_finetune)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the non-headline objects (variants, mpjpe, coherent_model, prox_window, perframe, ae_finetune)')
     ap.add_argument('--backend', choices=('nccl', 'gloo'), default='nccl', help='torch.distributed backend (nccl = RCCL; gloo only with --emu)')
     ap.add_argument('--emu', action='store_true',
                     help='DRY RUN of the multi-rank control flow without GPUs (tests/test_sharding.py): a reduced problem on the host-emulated '
                          'kernel library (liblemo_emu.so, CPU tensors), eager launches, no roofline / extras / CPU baseline -- the numbers '
                          'mean nothing; the barriers, the max-over-ranks timing, the one all-gather and the shard self-checks are the real ones')
     ap.add_argument('--concurrent-clips', type=int, default=3,
-                    help='after the headline measurement (one clip per GPU), also time this many independent clips fitted side by '
+                    help='with --full: after the headline measurement (one clip per GPU), also time this many independent clips fitted side by '
                          'side on GPU 0 (reported as "concurrent_clips", never as "value"; 0 = off)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / '
                          'float64, rank 0; the inputs are seeded: the same arguments give the same inputs on every run)')
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
     if args.model == 'coherent':
         from lemo_amd import synthetic as _syn
         _syn.DEFAULT_COHERENT = True
@@ -825,6 +839,48 @@ def main():
             dist.destroy_process_group()
         return
 
+    out = {
+        'metric': 'fitting-iterations/sec (T=120 frames)', 'value': world * args.steps / dt,
+        'unit': 'fitting-iterations/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': dt / args.steps * 1e3, 'ramp_iterations': ramp_iters, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f32', 'data': 'synthetic',
+        'config': {'workload': 'opt_amass_temp.py temporal fit, one TotalCapture-shaped clip per GPU: B=119 frames '
+                               '(the T=120 clip), SMPL-X-shaped synthetic model V=10475, VPoser decode, smoothness '
+                               'encoder 245x134, marker+contact+prior losses, Adam',
+                   'frames': B, 'vertices_per_frame': 10475 if not args.active_vertices_only else int(fit.n),
+                   'synthetic_model': args.model + (' (skinning joints i.i.d. per vertex: every 512-vertex chunk touches all 55 joints -- the worst case)'
+                                                     if args.model == 'iid' else ' (index locality of the licensed model: a 512-vertex chunk touches 4-17 joints)'),
+                   'sequences': world, 'conv_variant': fit.conv_variant,
+                   'arithmetic': arithmetic_label(fit.conv_variant),
+                   'parallelism': f'seq-shard x{world} + 1 all_gather', 'hip_graph': use_graph},
+        'final_total_loss': losses['total'],
+    }
+    if per_rank is not None:
+        out['per_rank_iterations_per_s'] = per_rank
+    if args.full:
+        out.update(full_measurements(args, fit, prob, stream, device, B, rank, world, use_graph))
+        if rank == 0 and world == 1 and not args.no_extras and use_graph:
+            # the other workloads of BASELINE.json on this GPU (never the headline value; a failure must not cost the line)
+            del fit
+            for key, fn in (('prox_window', lambda: prox_probe(device)[1]), ('perframe', lambda: perframe_probe(device)),
+                            ('ae_finetune', lambda: ae_probe(device))):
+                try:
+                    out[key] = fn()
+                except Exception as e:       # noqa: BLE001
+                    out[key] = {'error': f'{type(e).__name__}: {e}'}
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out['cpu_baseline'] = cpu_baseline(prob, B)
+            out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_measurements(args, fit, prob, stream, device, B, rank, world, use_graph):
+    """--full: what the line carries beyond the headline, measured on the headline's engine after its timed window: a second,
+    100-step window, the stage census, the roofline of the dominant kernel and of the vertex stage, and (rank 0, one GPU) the
+    concurrent clips, the kernel-family A/B, MPJPE against the oracle and the coherent model.  Returns the line's extra keys."""
     # a second, longer timed window of the same fit (world 1 only): the 20-step default window is 7 ms and the pool's boxes
     # differ by +-5 %; 100 steps is the reference's whole per-clip fit (opt_amass_temp.py:349)
     value_100 = None
@@ -843,7 +899,7 @@ def main():
         value_100 = 100.0 / (time.perf_counter() - t1)
 
     stage_us = None
-    if world == 1 and use_graph and gpu:
+    if world == 1 and use_graph:
         with torch.cuda.stream(stream):
             fit.step(40, use_graph=True)                    # clocks of the real kernel mix
             stage_us = fit.stage_census(20)
@@ -891,20 +947,6 @@ def main():
     # the backward epilogue (8.4 MB each) + 0.3 MB of weights: 25.5 MB forward, 33.9 MB backward, averaged over the 3 + 3 launches
     alg_bytes = (3 * 25.5e6 + 3 * 33.9e6) / 6.0 if pairs else 17.1e6
     out = {
-        'metric': 'fitting-iterations/sec (T=120 frames)', 'value': world * args.steps / dt,
-        'unit': 'fitting-iterations/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': dt / args.steps * 1e3, 'ramp_iterations': ramp_iters, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': 'f32', 'data': 'synthetic',
-        'config': {'workload': 'opt_amass_temp.py temporal fit, one TotalCapture-shaped clip per GPU: B=119 frames '
-                               '(the T=120 clip), SMPL-X-shaped synthetic model V=10475, VPoser decode, smoothness '
-                               'encoder 245x134, marker+contact+prior losses, Adam',
-                   'frames': B, 'vertices_per_frame': 10475 if not args.active_vertices_only else int(fit.n),
-                   'synthetic_model': args.model + (' (skinning joints i.i.d. per vertex: every 512-vertex chunk touches all 55 joints -- the worst case)'
-                                                     if args.model == 'iid' else ' (index locality of the licensed model: a 512-vertex chunk touches 4-17 joints)'),
-                   'sequences': world, 'conv_variant': fit.conv_variant,
-                   'arithmetic': arithmetic_label(fit.conv_variant),
-                   'parallelism': f'seq-shard x{world} + 1 all_gather', 'hip_graph': use_graph},
-        'final_total_loss': losses['total'],
         'roofline': {'bound': 'mfma', 'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s',
                      'frac': achieved / peak, 'traffic': pmc_traffic('lemo::conv3x3_pair_kernel<0' if pairs else
                                                                          'lemo::conv3x3_wino_kernel<0' if wino else
@@ -957,8 +999,6 @@ def main():
             'kernel_ms_back_to_back': vms_b2b,
             'blend_operands': 'two fp16 pieces each, pre-split (3 MFMA products per MAC)' if fit.dev.blend_f16 else 'three bf16 pieces each, split in the kernel (6 MFMA products per MAC)',
             'mfma_frac': vflops / (vms * 1e-3) / 1e12 / (PEAK_BF16_MATRIX_TFLOPS / (3.0 if fit.dev.blend_f16 else 6.0)), 'flop_per_launch': vflops}
-    if per_rank is not None:
-        out['per_rank_iterations_per_s'] = per_rank
     if rank == 0 and world == 1 and args.concurrent_clips > 1 and use_graph and not args.active_vertices_only:
         try:      # an extra, never the headline: a failure here must not cost the line
             out['concurrent_clips'] = concurrent_probe(fit, prob, B, device, args.concurrent_clips, max(args.steps, 100), args.conv_variant)
@@ -1018,22 +1058,7 @@ def main():
                         '512-vertex chunks, SDF sampling) does'}
         except Exception as e:       # noqa: BLE001
             out['coherent_model'] = {'error': f'{type(e).__name__}: {e}'}
-    if rank == 0 and world == 1 and not args.no_extras and use_graph:
-        # the other workloads of BASELINE.json on this GPU (never the headline value; a failure must not cost the line)
-        del fit
-        for key, fn in (('prox_window', lambda: prox_probe(device)[1]), ('perframe', lambda: perframe_probe(device)),
-                        ('ae_finetune', lambda: ae_probe(device))):
-            try:
-                out[key] = fn()
-            except Exception as e:       # noqa: BLE001
-                out[key] = {'error': f'{type(e).__name__}: {e}'}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out['cpu_baseline'] = cpu_baseline(prob, B)
-        out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == '__main__':

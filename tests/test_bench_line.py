@@ -82,3 +82,39 @@ def test_dump_outputs_prox_workload(tmp_path, emu_lib):
     assert d['steps'] == 2 and d['ms_per_step'] > 0
     assert a['params'].shape[0] == 1 and a['params'].dtype == np.float32 and np.isfinite(a['params']).all()
     assert float(a['total_loss']) == np.float32(d['total_loss'])
+
+
+# what only ``--full`` measures: a plain run carries none of it
+FULL_ONLY_KEYS = ('value_100_steps', 'stage_us', 'roofline', 'concurrent_clips', 'variants', 'mpjpe', 'mpjpe_mm', 'coherent_model',
+                  'prox_window', 'perframe', 'ae_finetune', 'cpu_baseline', 'speedup_vs_cpu_baseline')
+
+
+def test_full_is_off_by_default():
+    ap = _bench().arg_parser()
+    assert ap.parse_args([]).full is False
+    assert ap.parse_args(['--full']).full is True
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_run_is_the_headline_alone():
+    """``bench.py --gpus 1 --steps K --warmup W`` prints the headline line and does nothing beyond it"""
+    import json
+    import subprocess
+    import sys
+    import time
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    steps, warmup = 20, 5
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup)],
+                         capture_output=True, text=True, timeout=240, cwd=ROOT, env=env)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['metric'] == 'fitting-iterations/sec (T=120 frames)' and d['unit'] == 'fitting-iterations/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f32' and d['steps'] == steps and d['warmup'] == warmup and d['value'] > 0
+    assert abs(d['ms_per_step'] - 1e3 / d['value']) <= 1e-6 * d['ms_per_step']
+    assert not set(FULL_ONLY_KEYS) & set(d), sorted(set(FULL_ONLY_KEYS) & set(d))
+    print(f'\nplain bench run: {wall:.1f} s wall, {wall - (steps + warmup) * d["ms_per_step"] * 1e-3:.1f} s outside the steps')

@@ -10,5 +10,5 @@ done
 for so in "" lemo_amd/csrc/build_ab/*.so; do
   [ -z "$so" ] || [ -f "$so" ] || continue
   n=$([ -z "$so" ] && echo product || basename $so .so)
-  LEMO_HIP_LIB=$([ -z "$so" ] || echo $PWD/$so) timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench %-10s %.1f it/s  conv %.2f us' % ('$n', d['value'], d['roofline']['kernel_ms']*1e3))"
+  LEMO_HIP_LIB=$([ -z "$so" ] || echo $PWD/$so) timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench %-10s %.1f it/s  conv %.2f us' % ('$n', d['value'], d['roofline']['kernel_ms']*1e3))"
 done

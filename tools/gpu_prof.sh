@@ -2,7 +2,7 @@
 # parity tests + bench + rocprof kernel stats (no CPU baseline): quick per-kernel picture
 TAG=${1:-prof}; OUT=gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -6 > $OUT/pytest_gpu.log
-timeout 200 python bench.py --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench.json 2>> $OUT/bench.err
 cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$OUT/prof -o prof -- python $GRAFT_REPO_ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline > /dev/null 2> $GRAFT_REPO_ROOT/$OUT/prof.err
 cd $GRAFT_REPO_ROOT
 find $OUT/prof -name "*kernel_stats*" | head -1 | while read f; do cp "$f" $OUT/kernel_stats.csv; done

@@ -5,9 +5,9 @@ R=$GRAFT_REPO_ROOT
 timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -s -x -k "fused_pair or fit_full_size_golden" > $OUT/pytest_pair.log 2>&1; echo "pytest pair rc=$?" > $OUT/rc.txt
 timeout 300 python tools/pair_check.py > $OUT/pair_check.txt 2>&1
 for i in 1 2; do
-  for v in 5 4; do timeout 200 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras --conv-variant $v > $OUT/bench_100_v${v}_$i.json 2>> $OUT/bench.err; done
+  for v in 5 4; do timeout 200 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras --conv-variant $v > $OUT/bench_100_v${v}_$i.json 2>> $OUT/bench.err; done
 done
-timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_driver_style_1.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_driver_style_1.json 2>> $OUT/bench.err
 cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o prof -- python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras --ramp-ms 100 > $R/$OUT/bench_prof.json 2> $R/$OUT/prof.err
 cd $R
 find $OUT/prof -name "*kernel_stats*" | head -1 | while read f; do cp "$f" $OUT/kernel_stats.csv; done

@@ -21,10 +21,10 @@ cp $OUT/pmc/pmc_summary.json $OUT/pmc_summary.json 2>/dev/null
 cp $OUT/pmc_summary.json profiles/r02_pmc_summary.json 2>/dev/null
 rm -f $OUT/pmc/*.csv
 # 2. the driver's own command, three times + the 100-step run with the CPU baseline
-for i in 1 2 3; do timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --concurrent-clips 0 > $OUT/bench_driver_style_$i.json 2>> $OUT/bench.err; done
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
-timeout 400 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 > $OUT/bench_100.json 2>> $OUT/bench.err
-timeout 200 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --active-vertices-only > $OUT/bench_active.json 2>> $OUT/bench.err
+for i in 1 2 3; do timeout 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --concurrent-clips 0 > $OUT/bench_driver_style_$i.json 2>> $OUT/bench.err; done
+timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
+timeout 400 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 > $OUT/bench_100.json 2>> $OUT/bench.err
+timeout 200 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --active-vertices-only > $OUT/bench_active.json 2>> $OUT/bench.err
 # 3. kernel stats of the same command (rocprofv3 --kernel-trace --stats)
 cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/prof -o prof -- python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --ramp-ms 100 > $R/$OUT/bench_prof.json 2> $R/$OUT/prof.err
 cd $R

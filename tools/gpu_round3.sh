@@ -19,12 +19,12 @@ cp $OUT/pmc/pmc_summary.json $OUT/pmc_summary.json 2>/dev/null
 cp $OUT/pmc_summary.json profiles/r03_pmc_summary.json 2>/dev/null      # bench.py reads roofline.traffic from it (box-local copy)
 rm -f $OUT/pmc/*.csv
 # 2. the driver's own command (with everything: extras, concurrent clips, CPU baseline), twice more without the slow parts, 100 steps
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
 for i in 1 2; do timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_driver_style_$i.json 2>> $OUT/bench.err; done
-timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_100.json 2>> $OUT/bench.err
-timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras --conv-variant 3 > $OUT/bench_100_variant3_bf16x3.json 2>> $OUT/bench.err
-LEMO_BLEND_F16=0 timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_100_blend_bf16x3.json 2>> $OUT/bench.err
-timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_100_again.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_100.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras --conv-variant 3 > $OUT/bench_100_variant3_bf16x3.json 2>> $OUT/bench.err
+LEMO_BLEND_F16=0 timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_100_blend_bf16x3.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_100_again.json 2>> $OUT/bench.err
 timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras --active-vertices-only > $OUT/bench_active.json 2>> $OUT/bench.err
 timeout 400 python bench.py --workload prox --gpus 1 --steps 300 --warmup 100 > $OUT/bench_prox.json 2>> $OUT/bench.err
 # 3. kernel stats of the same command (rocprofv3 --kernel-trace --stats)

@@ -19,7 +19,7 @@ cp $OUT/pmc/pmc_summary.json $OUT/pmc_summary.json 2>/dev/null
 cp $OUT/pmc_summary.json profiles/r04_pmc_summary.json 2>/dev/null      # bench.py reads roofline.traffic from it (box-local copy)
 rm -f $OUT/pmc/*.csv $OUT/pmc_*.log
 # 2. the driver's own command (everything: stage census, variants, MPJPE, extras, concurrent clips, CPU baseline), then short ones
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_style.json 2>> $OUT/bench.err
 for i in 1 2; do timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_driver_style_$i.json 2>> $OUT/bench.err; done
 for i in 1 2; do
   timeout 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --concurrent-clips 0 --no-extras > $OUT/bench_100_$i.json 2>> $OUT/bench.err
