@@ -409,6 +409,42 @@ int lemo_wgrad3x3_batched(const float* A, long long a_stride, const float* B, lo
 int lemo_dec_end_fwd(const float* u, long long u_stride, const float* w8, const float* b8, const float* w9, const float* b9, float* r1,
                      float* rec, int bs, int H, int W, void* stream);
 
+/* ---- infilling-prior training: models/AE.py AE(downsample=True, in_channel=4, kernel=3), train_infill_prior.py:185-203
+ * (lemo_amd/csrc/ae_train_engine.hip).  One step on a batch of bs images with ONE parameter set:
+ *   x [bs][4][H][W]: the masked, reflect-padded network input; y [bs][H][W]: the unmasked padded target (channel 0); rec = AE(x);
+ *   L_body = mean |y - rec| over rows r < H - 5, L_v = mean |dy - drec| over the same rows and the W - 1 column differences,
+ *   L_c = BCEWithLogits(rec, y) over the 5 bottom rows; total = w_body L_body + w_v L_v + w_c L_c (train_infill_prior.py defaults
+ *   10, 10, 1); torch.optim.Adam(lr) with default betas / eps over all 40 tensors.  fp32 (fp32-input MFMA), every sum in a fixed
+ *   order: a graph replay, an eager run and a second engine give identical bits.
+ *   Shapes: 1 <= bs <= 128, H >= 6, W >= 2, H W <= 2^22 (lemo_aetrain_ws_floats returns 0 otherwise).  ws / ws_floats: caller-owned
+ *   ZEROED device workspace of lemo_aetrain_ws_floats(H, W, bs) floats, alive as long as the engine.  use_graph: capture the step
+ *   once, replay it.
+ * lemo_aetrain_load: flat = lemo_ae_n_param() floats (device) in lemo_ae_load's order; resets the optimizer.  Step / eval / params /
+ *   grads before a load: LEMO_ERR_STATE.
+ * lemo_aetrain_step: n >= 1 steps on (x, y); losses (device, may be NULL) <- {L_body, L_v, L_c, total} of the last step.
+ * lemo_aetrain_eval: the same losses under the current parameters, no update; rec (device, may be NULL) <- [bs][H][W].
+ * lemo_aetrain_params / _grads: the parameters / the last step's gradient (summed over the batch) in `flat` order.
+ * lemo_aetrain_pool_winners: the max-pool winners of encoder block `block` (0 .. 4) in the last forward, out (device) <- bs x
+ *   [C/8][Ho][Wo][8] bytes (C = the block's channels, Ho, Wo its pooled size), each the winning tap ky * 3 + kx of the 3 x 3 window
+ *   (first maximum in row-major order, as torch).  The max-pool adjoint routes every gradient through these. */
+typedef struct lemo_aetrain_desc {
+  int H, W, bs;
+  float lr;
+  float w_body, w_v, w_c;
+  float* ws;
+  long long ws_floats;
+  int use_graph;
+} lemo_aetrain_desc;
+long long lemo_aetrain_ws_floats(int H, int W, int bs);
+void* lemo_aetrain_create(const lemo_aetrain_desc* d);
+void lemo_aetrain_destroy(void* h);
+int lemo_aetrain_load(void* h, const float* flat, void* stream);
+int lemo_aetrain_step(void* h, const float* x, const float* y, int n, float* losses, void* stream);
+int lemo_aetrain_eval(void* h, const float* x, const float* y, float* losses, float* rec, void* stream);
+int lemo_aetrain_params(void* h, float* flat_out, void* stream);
+int lemo_aetrain_grads(void* h, float* flat_out, void* stream);
+int lemo_aetrain_pool_winners(void* h, int block, unsigned char* out, void* stream);
+
 /* ---- stream capture helpers: record everything a host-side step enqueues on `stream` (HIP kernels of this library
  * and the caller's own device work alike) into an executable graph, replay it with one call.  Relaxed capture mode;
  * the caller guarantees that the step does not synchronise and that every buffer it touches outlives the replays. */

@@ -73,6 +73,12 @@ class SptrainDesc(C.Structure):
                 ('weight_smooth', C.c_float), ('ws', vp), ('ws_floats', C.c_longlong), ('use_graph', C.c_int)]
 
 
+class AetrainDesc(C.Structure):
+    """lemo_aetrain_desc"""
+    _fields_ = [('H', C.c_int), ('W', C.c_int), ('bs', C.c_int), ('lr', C.c_float), ('w_body', C.c_float), ('w_v', C.c_float),
+                ('w_c', C.c_float), ('ws', vp), ('ws_floats', C.c_longlong), ('use_graph', C.c_int)]
+
+
 class SkinConst(C.Structure):
     _fields_ = [('V', C.c_int), ('NC', C.c_int), ('KW', C.c_int), ('blend_fp32', C.c_int)] + \
         [(n, vp) for n in ('Dg', 'v_template', 'w_idx', 'w_val', 'DgH')] + [('dgh_inv', C.c_float)]
@@ -264,6 +270,15 @@ _SIGS = {
     'lemo_wgrad3x3_batched_ws_floats': (C.c_longlong, [C.c_int] * 5),
     'lemo_wgrad3x3_batched': (C.c_int, [vp, C.c_longlong, vp, C.c_longlong] + [C.c_int] * 6 + [vp, vp, vp, vp]),
     'lemo_dec_end_fwd': (C.c_int, [vp, C.c_longlong, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp]),
+    'lemo_aetrain_ws_floats': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    'lemo_aetrain_create': (vp, [C.POINTER(AetrainDesc)]),
+    'lemo_aetrain_destroy': (None, [vp]),
+    'lemo_aetrain_load': (C.c_int, [vp, vp, vp]),
+    'lemo_aetrain_step': (C.c_int, [vp, vp, vp, C.c_int, vp, vp]),
+    'lemo_aetrain_eval': (C.c_int, [vp, vp, vp, vp, vp, vp]),
+    'lemo_aetrain_params': (C.c_int, [vp, vp, vp]),
+    'lemo_aetrain_grads': (C.c_int, [vp, vp, vp]),
+    'lemo_aetrain_pool_winners': (C.c_int, [vp, C.c_int, vp, vp]),
     'lemo_sdf_sample': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]),
     'lemo_fit_create': (vp, [C.POINTER(FitDesc)]),
     'lemo_fit_destroy': (None, [vp]),

@@ -19,6 +19,7 @@
 //   * loss gradient sign(rec - x) * mask / count in closed form (one launch, which also advances Adam's step counter and
 //     bias corrections on the device so that a captured step can be replayed).
 // Arithmetic: fp32 MFMA (v_mfma_f32_32x32x2_f32), every sum in a fixed order -> results do not depend on concurrency.
+#include "ae_engine.hpp"
 #include "conv_common.hpp"
 #include "conv_f16.hpp"
 
@@ -45,10 +46,7 @@ namespace lemo {
 // ---------------------------------------------------------------------------------------------------------------------
 // convolution, K split over the waves of the workgroup
 // ---------------------------------------------------------------------------------------------------------------------
-// A pixel (y, x) of the H x W grid the launch enumerates sits at padded pixel ((s y + 1) Wp + s x + 1) of a buffer with
-// row pitch Wp and stride s (1: plain CG8P of an H x W image; 2: the even pixels of a twice finer image = zero-stuffing
-// geometry).  Taps always address neighbouring pixels of the INPUT buffer.
-struct AeGeo { int H, W; int in_Wp, in_HWp, in_s; int out_Wp, out_HWp, out_s; int aux_Wp, aux_HWp, aux_s; };
+// (pixel geometry of a launch: AeGeo, ae_engine.hpp)
 
 // Clips side by side (round 4): an engine of K clips carves K identical workspaces, `cs` floats apart, and every
 // launch of a training step carries the clip as its last grid dimension -- the same kernels, the same launch shapes, K times the
@@ -57,6 +55,11 @@ struct AeGeo { int H, W; int in_Wp, in_HWp, in_s; int out_Wp, out_HWp, out_s; in
 #define AE_CLIP_OFFSET5(in_, wt_, bias_, aux_, out_, cs_)                                             \
   { const size_t o_ = (size_t)blockIdx.z * (cs_); in_ += o_; wt_ += o_; out_ += o_;                   \
     if (bias_) bias_ += o_; if (aux_) aux_ += o_; }
+// ... with the parameters (weights, bias) `wcs_` floats apart instead: the finetune engine passes its clip stride, the batched
+// trainer (ae_train_engine.hip) 0 -- one parameter set shared by every image of the batch
+#define AE_CLIP_OFFSET6(in_, wt_, bias_, aux_, out_, cs_, wcs_)                                       \
+  { const size_t o_ = (size_t)blockIdx.z * (cs_), w_ = (size_t)blockIdx.z * (wcs_); in_ += o_; wt_ += w_; out_ += o_; \
+    if (bias_) bias_ += w_; if (aux_) aux_ += o_; }
 
 // maximum of |v| over the wave's stored lanes -> the launch's slot (bit pattern of a non-negative float orders like the float)
 // (one atomic per wave on ONE word cost a launch ~11 ns each -- 2.7 k waves = the whole 29 us of a launch, which is how the first version
@@ -72,9 +75,9 @@ __device__ __forceinline__ void ae_amax_publish(float m, float* slot) {
 template <int MT, int EPI>          // MT x 32 couts per workgroup; EPI: conv_common.hpp (0 lrelu(acc + bias), 1 acc * lrelu'(aux), 2 acc + bias)
 __global__ void __launch_bounds__(1024)
 ae_conv_kernel(const float* __restrict__ in, const float* __restrict__ wt, const float* __restrict__ bias,
-               const float* __restrict__ aux, float* __restrict__ out, AeGeo g, int cin_lg, int cout, int pt_lg, size_t cs,
+               const float* __restrict__ aux, float* __restrict__ out, AeGeo g, int cin_lg, int cout, int pt_lg, size_t cs, size_t wcs,
                float* __restrict__ amax_out /* may be null: max |out| of the launch, for a split-f16 consumer (ae_conv_f16_kernel) */) {
-  AE_CLIP_OFFSET5(in, wt, bias, aux, out, cs);                 // clip = blockIdx.z: every operand lives in that clip's workspace
+  AE_CLIP_OFFSET6(in, wt, bias, aux, out, cs, wcs);            // clip = blockIdx.z: every operand lives in that clip's workspace
   if (amax_out) amax_out += (size_t)blockIdx.z * cs;
   LEMO_DYN_SMEM(red);                                          // [wave][MT][4][64 lanes] float4
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), NW = blockDim.x >> 6;   // (scalar: see the ring below)
@@ -183,8 +186,8 @@ ae_conv_kernel(const float* __restrict__ in, const float* __restrict__ wt, const
 template <int EPI>
 __global__ void __launch_bounds__(1024)
 ae_conv16_kernel(const float* __restrict__ in, const float* __restrict__ wt, const float* __restrict__ bias,
-                 const float* __restrict__ aux, float* __restrict__ out, AeGeo g, int cin_lg, int cout, int pt_lg, size_t cs) {
-  AE_CLIP_OFFSET5(in, wt, bias, aux, out, cs);
+                 const float* __restrict__ aux, float* __restrict__ out, AeGeo g, int cin_lg, int cout, int pt_lg, size_t cs, size_t wcs) {
+  AE_CLIP_OFFSET6(in, wt, bias, aux, out, cs, wcs);
   LEMO_DYN_SMEM(red);                                          // [wave][64 lanes] float4
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), NW = blockDim.x >> 6;
   const int PT = 1 << pt_lg, pt = wave & (PT - 1), ks = wave >> pt_lg, KS = NW >> pt_lg;
@@ -256,8 +259,6 @@ ae_conv16_kernel(const float* __restrict__ in, const float* __restrict__ wt, con
   }
   st4(out + o, v);
 }
-
-static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // the same convolutions on the f16 matrix cores ("split-f16", round 6): built, parity-tested, SELECTABLE, not the
@@ -553,8 +554,10 @@ static void ae_conv_shape(int P, int cin, int cout, int nclip, int* mt_out, int*
 
 // f16 != nullptr (and cin >= 16): the split-f16 kernels with the scales of *f16; else the fp32-input MFMA kernels
 int ae_conv(const float* in, const float* wt, const float* bias, const float* aux, float* out, const AeGeo& g, int cin, int cout,
-            int epi, hipStream_t s, int force_mt = 0, int force_pt = 0, int force_ks = 0, int nclip = 1, size_t cs = 0, const AeF16* f16 = nullptr) {
+            int epi, hipStream_t s, int force_mt, int force_pt, int force_ks, int nclip, size_t cs, const AeF16* f16, size_t wcs) {
   if (cin % 8 || (cin & (cin - 1)) || cout % 32 || g.H < 1 || g.W < 1 || epi < 0 || epi > 2) return LEMO_ERR_SHAPE;
+  if (wcs == AE_WCS_CLIP) wcs = cs;
+  if (f16 && wcs != cs) return LEMO_ERR_ARG;                  // (the split-f16 kernels keep per-clip parameters)
   float* amax_only = nullptr;                                 // fp32-input kernel that still publishes max |out| for its split-f16 consumer
   if (f16 && cin < 16) { amax_only = f16->amax_out; f16 = nullptr; }      // the 8-channel first layer keeps the fp32-input kernel (2 % of a step's flops)
   if (f16 && (!f16->amax_in || !f16->wmax || !f16->amax_out)) return LEMO_ERR_ARG;
@@ -587,7 +590,7 @@ int ae_conv(const float* in, const float* wt, const float* bias, const float* au
     if (cin < 16 || ks > 9 * (cin / 16)) return LEMO_ERR_ARG;
     const dim3 grid(((g.H * g.W + 15) / 16 + pt - 1) / pt, cout / 16, nclip);
     const size_t lds = (size_t)nw * 1024;
-#define LAUNCH16(EPI_) hipLaunchKernelGGL((ae_conv16_kernel<EPI_>), grid, dim3(64 * nw), lds, s, in, wt, bias, aux, out, g, lg, cout, pt_lg, cs)
+#define LAUNCH16(EPI_) hipLaunchKernelGGL((ae_conv16_kernel<EPI_>), grid, dim3(64 * nw), lds, s, in, wt, bias, aux, out, g, lg, cout, pt_lg, cs, wcs)
     if (epi == 0) LAUNCH16(0); else if (epi == 1) LAUNCH16(1); else LAUNCH16(2);
 #undef LAUNCH16
     return (int)hipGetLastError();
@@ -595,7 +598,7 @@ int ae_conv(const float* in, const float* wt, const float* bias, const float* au
   if ((mt != 1 && mt != 2) || cout % (32 * mt) || nw * mt > 16 || ks > 9 * (cin / 8)) return LEMO_ERR_ARG;
   const dim3 grid(((g.H * g.W + 31) / 32 + pt - 1) / pt, cout / (32 * mt), nclip);
   const size_t lds = (size_t)nw * mt * 4096;
-#define LAUNCH(MT_, EPI_) hipLaunchKernelGGL((ae_conv_kernel<MT_, EPI_>), grid, dim3(64 * nw), lds, s, in, wt, bias, aux, out, g, lg, cout, pt_lg, cs, amax_only)
+#define LAUNCH(MT_, EPI_) hipLaunchKernelGGL((ae_conv_kernel<MT_, EPI_>), grid, dim3(64 * nw), lds, s, in, wt, bias, aux, out, g, lg, cout, pt_lg, cs, wcs, amax_only)
   if (mt == 2) { if (epi == 0) LAUNCH(2, 0); else if (epi == 1) LAUNCH(2, 1); else LAUNCH(2, 2); }
   else         { if (epi == 0) LAUNCH(1, 0); else if (epi == 1) LAUNCH(1, 1); else LAUNCH(1, 2); }
 #undef LAUNCH
@@ -622,12 +625,10 @@ int ae_conv(const float* in, const float* wt, const float* bias, const float* au
 // With ci on the MFMA's row axis a lane holds 4 consecutive ci of one co per accumulator quad: the slab partial is stored with
 // dwordx4 stores, 1 KiB contiguous per wave, directly in the forward pack wt[tap][ci/8][co][8] -- the layout of the parameter
 // vector, so the optimizer reads it with unit stride.
-#define AE_SLAB 576               // padded pixels per slab, at most (a layer's slabs are equal parts: ae_slabs)
 struct AeWgradJob {
   const float* dy; const float* x; float* partial; float* dbp;       // dbp: [nslab][2][cout] bias-gradient partials (pixel parity kept apart)
   int H, W; int cin, cout, nslab, slab_len, nwave;
 };
-#define AE_NLAYER 20
 // the grid is the layers' waves in the order the host wants them DISPATCHED: the long ones first (full 576-pixel slabs run 23 us),
 // the short ones of the 14 x 9 layers last, so that the launch does not end on a few long waves
 struct AeWgradJobs { AeWgradJob j[AE_NLAYER]; int first[AE_NLAYER + 1]; int n; size_t cs; };       // cs: clip stride (clip = blockIdx.y)
@@ -746,14 +747,6 @@ ae_wgrad_multi_kernel(AeWgradJobs J) {
 // theta = [weights of layer 0 | ... | weights of layer 19 | biases of layer 0 | ... ], weights in the forward pack
 // wt[tap][cin_pad/8][cout_pad][8] (each a multiple of 256 floats: a block never straddles layers), biases padded to
 // cout_pad.  Padded entries have zero gradient (their operands are zero) and are masked here as well, so they stay zero.
-struct AeAdamLayer { const float* partial; const float* dbp; int nslab, w_off, b_off, wb_off, cin_lg /*log2(cin_pad/8)*/, cout_lg, cin, cout; };
-struct AeAdamArgs {
-  AeAdamLayer L[AE_NLAYER];
-  float* theta; float* m; float* v; float* wb; const float* ctr;    // ctr: [1] = -lr / (1 - b1^t), [2] = sqrt(1 - b2^t) (floats)
-  float* amax;                                                      // the step's tensor maxima: slots 0 .. AE_SLOT_DYN - 1 zeroed here for the next step
-  int n_w, n_all; float lr;
-  size_t cs;                                                        // clip stride (clip = blockIdx.y)
-};
 
 __device__ __forceinline__ float adam_update(float p, float g, float& m, float& v, AdamCoef c) {
   adam_update_torch(p, m, v, g, c);                                 // common.hpp: torch.optim.Adam's own evaluation order
@@ -889,8 +882,6 @@ ae_from_cg8p_kernel(const float* __restrict__ src, int C, int H, int W, float* _
 // the model's own tensors (state_dict order: per layer weight then bias; Conv2d weight [out][in][3][3], ConvTranspose2d
 // weight [in][out][3][3]) <-> theta (+ the backward pack).  The conv-equivalent weight of a stride-1 transposed convolution
 // is the flipped transpose: cw[co][ci][tap] = w[ci][co][8 - tap].
-struct AePackLayer { int w_off, wb_off, b_off, flat_w, flat_b, cin_lg, cout_lg, cin, cout, deconv; };
-struct AePackArgs { AePackLayer L[AE_NLAYER]; int n_w, n_all; };
 
 __device__ __forceinline__ int ae_flat_index(const AePackLayer& q, int tap, int ci, int co) {
   return q.deconv ? q.flat_w + (ci * q.cout + co) * 9 + (8 - tap) : q.flat_w + (co * q.cin + ci) * 9 + tap;
@@ -931,32 +922,19 @@ ae_pack_kernel(AePackArgs A, const float* __restrict__ src, float* __restrict__ 
   }
 }
 
+int ae_adam_launch(const AeAdamArgs& A, int nclip, hipStream_t s) {
+  hipLaunchKernelGGL(ae_adam_kernel, dim3((A.n_all / 4 + 255) / 256, nclip), dim3(256), 0, s, A);        // (n_w and n_b are multiples of 4)
+  return (int)hipGetLastError();
+}
+int ae_pack_launch(const AePackArgs& A, bool unpack, const float* src, float* dst, float* wb, hipStream_t s) {
+  if (unpack) hipLaunchKernelGGL((ae_pack_kernel<true>), dim3((A.n_all + 255) / 256), dim3(256), 0, s, A, src, dst, (float*)nullptr);
+  else hipLaunchKernelGGL((ae_pack_kernel<false>), dim3((A.n_all + 255) / 256), dim3(256), 0, s, A, src, dst, wb);
+  return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // the engine
 // ---------------------------------------------------------------------------------------------------------------------
-static const int AE_ENC[5][2] = {{4, 32}, {32, 64}, {64, 128}, {128, 256}, {256, 256}};      // models/AE.py:81-91, in_channel = 4
-static const int AE_DEC[5][2] = {{256, 256}, {256, 128}, {128, 64}, {64, 32}, {32, 1}};
-
-struct AeLayer { int cin, cout, cin_pad, cout_pad, deconv, level, w_off, b_off, wb_off, flat_w, flat_b, nslab, slab_len; size_t part_off, dbp_off; };
-
-// slabs of padded interior pixels for the weight gradients: equal parts of at most AE_SLAB pixels, a multiple of 32 long (27 x 19
-// = 513 padded pixels is ONE slab, not 512 + 1)
-// `scale` (round 5, measured and NOT adopted): with k clips side by side the launch has k x the waves, so a clip's slabs could be k x
-// longer for the same number of waves in flight (fewer partial tiles written by the weight-gradient launch and read back by the
-// optimiser launch).  8 clips per engine, ms per clip: x1 16.40, x2 16.69, x4 17.24, x8 18.07, x16 20.51; 16 clips: x1 15.43, x4 15.76,
-// x8 16.32 (profiles/r05_ab_ae_slab_scale.txt) -- the launch wants MANY SHORT waves (its cost is the spread between a level-0 wave
-// and a level-4 one, not the 40 MB of partials per clip), so the scale stays 1; LEMO_AE_SLAB_SCALE keeps the switch
-static int ae_slabs(int H, int W, int* len, int scale = 1) {
-  const int cap = AE_SLAB * (scale < 1 ? 1 : scale);
-  const int n_px = H * (W + 2), n = (n_px + cap - 1) / cap;
-  *len = ((n_px + n - 1) / n + 31) / 32 * 32;
-  return (n_px + *len - 1) / *len;
-}
-
-static int pad8(int c) { return (c + 7) / 8 * 8; }
-static int pad32(int c) { return (c + 31) / 32 * 32; }
-static size_t cg8p_floats(int C, int H, int W) { return (size_t)(C / 8 > 0 ? C / 8 : 1) * (H + 2) * (W + 2) * 8; }
-
 struct AeEngine {
   int H[6], W[6];
   AeLayer L[AE_NLAYER];
@@ -981,15 +959,6 @@ struct AeEngine {
                                // (profiles/r06_ae_f16_vs_fp32.txt): 16.05 vs 16.4 ms per clip at 8 clips per engine, 14.4 vs 15.45 at 16, but 44.5 vs
                                // 28.8 for a solo clip -- the launches are bound by L2 re-reads of the direct-from-global operands (every input element
                                // 9 taps x cout / 32 MT times) and per-wave latency, not by the matrix pipe: SQ_VALU_MFMA_BUSY 9 % (f16) / 48 % (fp32)
-};
-
-
-// every buffer is wrapped in AE_GUARD zeroed floats that nothing writes: the weight-gradient kernel's operand windows may
-// reach up to 17 pixels (136 floats) past either end of a CG8P buffer, at positions whose products are multiplied by zero
-#define AE_GUARD 256
-struct Bump {
-  float* base; size_t off = 0;
-  float* take(size_t n) { float* p = base ? base + off + AE_GUARD : nullptr; off += (n + 2 * AE_GUARD + 63) / 64 * 64; return p; }
 };
 
 // the same routine sizes the workspace (base == nullptr) and carves it
@@ -1059,8 +1028,6 @@ static void ae_layout(AeEngine* e, int H0, int W0, float* base, size_t* total, i
   for (int i = 0; i < AE_NLAYER; ++i) e->dp[i] = B.take(cg8p_floats(e->L[i].cout_pad, e->H[e->L[i].level], e->W[e->L[i].level]));
   *total = B.off;
 }
-
-static AeGeo geo_plain(int H, int W) { const int Wp = W + 2, HWp = (H + 2) * Wp; return AeGeo{H, W, Wp, HWp, 1, Wp, HWp, 1, Wp, HWp, 1}; }
 
 // engine launches carry every clip: ae_conv(..., s) -> ae_conv(..., s, 0, 0, 0, e->nclip, e->cs)
 #define AE_CONV(e_, ...) ae_conv(__VA_ARGS__, 0, 0, 0, (e_)->nclip, (e_)->cs)

@@ -1,0 +1,245 @@
+"""Native training of the motion infilling prior: ``models/AE.py::AE(downsample=True, in_channel=4, kernel=3)`` as
+``train_infill_prior.py:185-203`` trains it (``body_mode='local_markers_4chan'``), on the ``lemo_aetrain_*`` engine
+(include/lemo_hip.h).
+
+Per step, for the masked input ``clip_img_input`` and the target ``clip_img`` (both ``[bs, 4, d, T]``):
+``x = reflect_pad(clip_img_input, (8, 8, 1, 1))``, ``y = reflect_pad(clip_img, (8, 8, 1, 1))[:, 0]``, ``rec = AE(x)``,
+``loss = w_body * l1(y[:, :-5], rec[:, :-5]) + w_v * l1(dy[:, :-5], drec[:, :-5]) + w_c * bce_with_logits(rec[:, -5:], y[:, -5:])``
+(``d``: differences of neighbouring frames), one ``torch.optim.Adam(lr)`` step over all 40 tensors.  Data loading and the RNG
+stay the caller's: the two masking recipes of the reference are the pure torch helpers below.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _hip
+from ._hip import ptr
+from .infill import _layers
+
+PAD = (8, 8, 1, 1)
+LEFT_FOOT, RIGHT_FOOT = (16, 30), (47, 60)
+"""marker ids whose masking also masks the left / right foot-contact rows (train_infill_prior.py:154-159)"""
+
+
+def param_layout() -> List[Tuple[str, Tuple[int, ...]]]:
+    """(key, shape) of the 40 tensors in the engine's flat order (state_dict order, lemo_ae_load's order)"""
+    out = []
+    for l in _layers():
+        out += [(l.name + '.weight', (l.cin, l.cout, 3, 3) if l.deconv else (l.cout, l.cin, 3, 3)), (l.name + '.bias', (l.cout,))]
+    return out
+
+
+def n_param() -> int:
+    return sum(int(np.prod(s)) for _, s in param_layout())
+
+
+def flatten_state(sd: Dict) -> np.ndarray:
+    parts = []
+    for k, shp in param_layout():
+        v = sd[k]
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        if tuple(v.shape) != shp:
+            raise ValueError(f'{k}: shape {tuple(v.shape)}, expected {shp}')
+        parts.append(np.ascontiguousarray(v, np.float32).ravel())
+    return np.concatenate(parts)
+
+
+def unflatten_state(flat) -> Dict[str, torch.Tensor]:
+    flat = flat.numpy() if torch.is_tensor(flat) else np.asarray(flat)
+    sd, o = {}, 0
+    for k, shp in param_layout():
+        n = int(np.prod(shp))
+        sd[k] = torch.from_numpy(np.array(flat[o:o + n], np.float32).reshape(shp))
+        o += n
+    return sd
+
+
+def default_ae_state(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """torch's default Conv2d / ConvTranspose2d initialisation bounds (kaiming-uniform a = sqrt(5): 1 / sqrt(fan_in) for weights
+    and biases; fan_in = weight.shape[1] * 9, which for ConvTranspose2d is its OUTPUT channel count), drawn from
+    numpy.random.default_rng(seed) in state_dict order, so a seed gives the same weights on every torch version"""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for k, shp in param_layout():
+        if k.endswith('.weight'):
+            bound = 1.0 / np.sqrt(shp[1] * 9)
+        else:
+            wshape = sd[k[:-len('bias')] + 'weight'].shape
+            bound = 1.0 / np.sqrt(wshape[1] * 9)
+        sd[k] = torch.from_numpy(rng.uniform(-bound, bound, size=shp).astype(np.float32))
+    return sd
+
+
+def network_tensors(clip_img_input: torch.Tensor, clip_img: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """([bs, 4, d, T] masked input, [bs, 4, d, T] target) -> (x [bs, 4, d + 2, T + 16], y [bs, d + 2, T + 16])"""
+    x = F.pad(clip_img_input.float(), PAD, 'reflect').contiguous()
+    y = F.pad(clip_img.float(), PAD, 'reflect')[:, 0].contiguous()
+    return x, y
+
+
+def mask_random_markers(clip_img: torch.Tensor, marker_ids: torch.Tensor) -> torch.Tensor:
+    """train_infill_prior.py:135-160: a masked copy of clip_img [bs, 4, d, T]; marker_ids [bs, n] long (the caller draws them:
+    ``(torch.rand(bs, n) * 67).long()``).  Zeroes channel 0's 3 rows of each marker (after the 3 pelvis rows) and the foot-contact
+    rows -4 / -2 (ids 16, 30) and -3 / -1 (ids 47, 60)."""
+    out = clip_img.clone()
+    rows = marker_ids.long() * 3 + 3
+    for i in range(clip_img.shape[0]):
+        for r in (rows[i], rows[i] + 1, rows[i] + 2):
+            out[i, 0, r, :] = 0.
+        ids = marker_ids[i].tolist()
+        if LEFT_FOOT[0] in ids or LEFT_FOOT[1] in ids:
+            out[i, 0, -4, :] = 0.
+            out[i, 0, -2, :] = 0.
+        if RIGHT_FOOT[0] in ids or RIGHT_FOOT[1] in ids:
+            out[i, 0, -3, :] = 0.
+            out[i, 0, -1, :] = 0.
+    return out
+
+
+def load_prox_mask_clips(mask_dir: str, clip_len: int = 120, min_ratio: float = 0.05) -> np.ndarray:
+    """train_infill_prior.py:116-127: every ``<mask_dir>/<seq>/mask_markers.npy`` ([T, 67], 0 = masked) cut into clip_len-frame
+    clips; a clip is kept when at least min_ratio of its entries are masked.  -> [n, clip_len, 67 * 3] (each marker's column
+    repeated for its 3 rows)"""
+    out = []
+    for d in sorted(os.listdir(mask_dir)):
+        mask = np.load(os.path.join(mask_dir, d, 'mask_markers.npy'))
+        for i in range(len(mask) // clip_len):
+            mc = mask[i * clip_len:(i + 1) * clip_len]
+            n_all = mc.shape[0] * mc.shape[1]
+            if (n_all - mc.sum()) / n_all >= min_ratio:
+                out.append(np.repeat(mc, 3, axis=1))
+    return np.asarray(out)
+
+
+def mask_prox(clip_img: torch.Tensor, mask_clips) -> torch.Tensor:
+    """train_infill_prior.py:162-178: clip_img [bs, 4, d, T] with channel 0 multiplied by the PROX masks mask_clips [bs, L, 67 * 3]
+    (L >= T; the caller shuffles and picks them), the pelvis rows kept and the foot-contact rows masked where either marker of that
+    foot is"""
+    bs, T = clip_img.shape[0], clip_img.shape[-1]
+    m = torch.as_tensor(np.asarray(mask_clips)).float().permute(0, 2, 1).unsqueeze(1).to(clip_img.device)     # [bs, 1, 201, L]
+    left = (m[:, :, 16 * 3:16 * 3 + 1] == 1) * (m[:, :, 30 * 3:30 * 3 + 1] == 1)
+    right = (m[:, :, 47 * 3:47 * 3 + 1] == 1) * (m[:, :, 60 * 3:60 * 3 + 1] == 1)
+    contact = torch.cat([left, right, left, right], dim=-2).float()
+    full = torch.cat([torch.ones(bs, 1, 3, T, device=clip_img.device), m[..., 0:T], contact[..., 0:T]], dim=-2)
+    out = clip_img.clone()
+    out[:, 0:1] = out[:, 0:1] * full
+    return out
+
+
+class InfillPriorTrainer:
+    """AE training steps on the native engine.  ``batch``, ``H``, ``W``: the batch size and the NETWORK input size (d + 2, T + 16:
+    210 x 135 for 67 markers and 119 frames).  ``state_dict=None`` starts from ``default_ae_state(seed)``."""
+
+    def __init__(self, state_dict: Optional[Dict] = None, batch: int = 60, H: int = 210, W: int = 135, lr: float = 1e-4,
+                 weight_loss_rec_body: float = 10., weight_loss_rec_body_v: float = 10., weight_loss_rec_contact_lbl: float = 1.,
+                 seed: int = 0, device=None, use_graph: bool = True, _lib=None):
+        self.lib = _lib or _hip.get_lib()
+        if device is None:
+            device = torch.device('cpu') if self.lib.is_emu else torch.device('cuda', torch.cuda.current_device())
+        self.device = torch.device(device)
+        self.bs, self.H, self.W = int(batch), int(H), int(W)
+        self.h = None
+        nws = self.lib.aetrain_ws_floats(self.H, self.W, self.bs)
+        if nws <= 0:
+            raise ValueError(f'infilling-prior training does not take batch {batch} at {H} x {W} '
+                             f'(1 <= batch <= 128, H >= 6, W >= 2, H * W <= 2^22)')
+        self.stream = None if self.lib.is_emu else torch.cuda.Stream(self.device)
+        self.ws = torch.zeros(int(nws), dtype=torch.float32, device=self.device)
+        d = _hip.AetrainDesc(H=self.H, W=self.W, bs=self.bs, lr=float(lr), w_body=float(weight_loss_rec_body),
+                             w_v=float(weight_loss_rec_body_v), w_c=float(weight_loss_rec_contact_lbl), ws=ptr(self.ws),
+                             ws_floats=int(nws), use_graph=int(bool(use_graph) and not self.lib.is_emu))
+        self.h = self.lib.aetrain_create(ctypes.byref(d))
+        if not self.h:
+            raise _hip.LemoHipError('lemo_aetrain_create failed')
+        if state_dict is None:
+            state_dict = default_ae_state(seed)
+        flat = torch.from_numpy(flatten_state(state_dict)).to(self.device)
+        self._losses = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._call(lambda s: self.lib.check(self.lib.aetrain_load(self.h, ptr(flat), s), 'aetrain_load'))
+
+    def _call(self, fn):
+        if self.stream is None:
+            return fn(None)
+        cur = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(cur)
+        try:
+            return fn(self.stream.cuda_stream)
+        finally:
+            cur.wait_stream(self.stream)
+
+    def _xy(self, clip_img_input, clip_img, prepared):
+        for t in (clip_img_input, clip_img):
+            if not torch.is_tensor(t):
+                raise TypeError('clip images must be torch tensors')
+            if t.device != self.device:
+                raise ValueError(f'clip images must live on {self.device}, got {t.device}')
+        if prepared:
+            x, y = clip_img_input.float().contiguous(), clip_img.float().contiguous()
+        else:
+            if clip_img_input.dim() != 4 or clip_img_input.shape[1] != 4 or clip_img.shape != clip_img_input.shape:
+                raise ValueError(f'expected two [bs, 4, d, T] clip images, got {tuple(clip_img_input.shape)} and {tuple(clip_img.shape)}')
+            x, y = network_tensors(clip_img_input, clip_img)
+        if tuple(x.shape) != (self.bs, 4, self.H, self.W) or tuple(y.shape) != (self.bs, self.H, self.W):
+            raise ValueError(f'network input {tuple(x.shape)} / target {tuple(y.shape)}, the trainer was built for '
+                             f'{(self.bs, 4, self.H, self.W)} / {(self.bs, self.H, self.W)}')
+        return x, y
+
+    def step(self, clip_img_input: torch.Tensor, clip_img: torch.Tensor, n: int = 1, prepared: bool = False) -> Tuple[float, float, float]:
+        """n training steps -> (loss_rec_body, loss_rec_body_v, loss_rec_contact_lbl) of the last step.  prepared=True: the inputs
+        are already the padded network input x [bs, 4, H, W] and target y [bs, H, W]"""
+        x, y = self._xy(clip_img_input, clip_img, prepared)
+        self._call(lambda s: self.lib.check(self.lib.aetrain_step(self.h, ptr(x), ptr(y), int(n), ptr(self._losses), s), 'aetrain_step'))
+        l = self._losses.cpu()
+        return float(l[0]), float(l[1]), float(l[2])
+
+    def evaluate(self, clip_img_input: torch.Tensor, clip_img: torch.Tensor, return_rec: bool = False, prepared: bool = False):
+        """the same losses under the current parameters, no update; return_rec: also the reconstruction [bs, 1, H, W]"""
+        x, y = self._xy(clip_img_input, clip_img, prepared)
+        rec = torch.empty(self.bs, self.H, self.W, dtype=torch.float32, device=self.device) if return_rec else None
+        self._call(lambda s: self.lib.check(self.lib.aetrain_eval(self.h, ptr(x), ptr(y), ptr(self._losses), ptr(rec), s), 'aetrain_eval'))
+        l = self._losses.cpu()
+        out = (float(l[0]), float(l[1]), float(l[2]))
+        return (out + (rec[:, None],)) if return_rec else out
+
+    def last_total(self) -> float:
+        return float(self._losses[3].cpu())
+
+    def flat_params(self) -> torch.Tensor:
+        out = torch.empty(n_param(), dtype=torch.float32, device=self.device)
+        self._call(lambda s: self.lib.check(self.lib.aetrain_params(self.h, ptr(out), s), 'aetrain_params'))
+        return out.cpu()
+
+    def flat_grads(self) -> torch.Tensor:
+        """the gradient of the last training step (summed over the batch), in the flat order"""
+        out = torch.empty(n_param(), dtype=torch.float32, device=self.device)
+        self._call(lambda s: self.lib.check(self.lib.aetrain_grads(self.h, ptr(out), s), 'aetrain_grads'))
+        return out.cpu()
+
+    def pool_winners(self) -> List[torch.Tensor]:
+        """the max-pool winners of the five encoder blocks in the last forward: [bs, C, Ho, Wo] uint8 taps ky * 3 + kx each"""
+        out, h, w = [], self.H, self.W
+        for b, c in enumerate((32, 64, 128, 256, 256)):
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            t = torch.empty(self.bs * c * h * w, dtype=torch.uint8, device=self.device)
+            self._call(lambda s: self.lib.check(self.lib.aetrain_pool_winners(self.h, b, ptr(t), s), 'aetrain_pool_winners'))
+            out.append(t.view(self.bs, c // 8, h, w, 8).permute(0, 1, 4, 2, 3).reshape(self.bs, c, h, w).cpu())
+        return out
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """the parameters as CPU tensors under the reference's keys (enc_blc1.main.0.weight ... dec_blc5.deconv2.bias)"""
+        return unflatten_state(self.flat_params())
+
+    def close(self):
+        if getattr(self, 'h', None):
+            _hip.quiesce(self.device, self.lib)
+            self.lib.aetrain_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
