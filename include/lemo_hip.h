@@ -445,6 +445,67 @@ int lemo_aetrain_params(void* h, float* flat_out, void* stream);
 int lemo_aetrain_grads(void* h, float* flat_out, void* stream);
 int lemo_aetrain_pool_winners(void* h, int block, unsigned char* out, void* stream);
 
+/* ---- the loop level of both training engines: a whole epoch of DIFFERENT batches with the dataset on the device
+ * (lemo_amd/csrc/train_epoch_kernels.hip).  For s = 0 .. n_steps - 1: one kernel assembles batch s from the device-resident clips
+ * straight into the engine's staging buffers, the engine runs one step (train != 0) or forward + losses (train == 0: the
+ * reference's test-loss loop; the caller averages), and the step's losses go to row s of `log` (device, caller-owned: AE
+ * {L_body, L_v, L_c, total}, smoothness {L1, smooth, total}).  The host never waits between steps; with use_graph ONE captured
+ * chain (assemble, step, log) is replayed n_steps times: the step cursor lives in device memory.  Same kernels and bits as
+ * n_steps lemo_*train_step calls on the same batches.
+ * Infilling prior: data [n_clips][4][H-2][W-16] (the unpadded clip images), idx [n_steps][bs] int32.  Batch s is
+ *   x = reflect_pad(mask(clip), (8, 8, 1, 1)), y = reflect_pad(clip)[:, 0]; the mask (channel 0 only, before the padding) is
+ *   LEMO_MASK_NONE:   none (input = target);
+ *   LEMO_MASK_RANDOM: marker_ids [n_steps][bs][6] int32 in -1 .. 66 (-1: unused slot): rows 3 + 3 id .. + 2 set to 0; rows d-4 and
+ *                     d-2 if 16 or 30 is among the slot's ids, rows d-3 and d-1 if 47 or 60 is (train_infill_prior.py:135-160);
+ *   LEMO_MASK_PROX:   masks [n_masks][67][mask_len] fp32 (marker-major, frame fastest; mask_len >= W - 16, frames 0 .. W-17 are
+ *                     used), mask_idx [n_steps][bs] int32: the 3 pelvis rows x 1, each marker's 3 rows x its mask, the contact
+ *                     rows x (both markers of that foot == 1) (train_infill_prior.py:162-178).
+ *   The masking recipes need H - 2 == 208 (67 markers).  W >= 25.
+ * Smoothness prior: data [n_clips][1][H-2][W-15]; batch s is reflect_pad(clip[..., 1:] - clip[..., :-1], (8, 8, 1, 1)).  W >= 25, H >= 4.
+ * Every index is the CALLER's to validate (0 <= idx < n_clips, -1 <= id < 67, 0 <= mask_idx < n_masks): the tables live on the
+ * device (the kernels clamp clip and mask indices into range so that a bad table cannot read outside the buffers).
+ * LEMO_ERR_ARG: null pointers, counts < 1, a shape that does not fit the recipe; LEMO_ERR_STATE: _epoch before a load.
+ * lemo_*train_batch: batch `step` of the same descriptor in the API layout (x [bs][4][H][W], y [bs][H][W]; smoothness x [bs][H][W])
+ *   through the same device function, for inspection and tests (`log`, `train` unused).
+ * Training state: lemo_*train_state_floats() = 3 P + 2 floats (P = lemo_ae_n_param() / lemo_sptrain_n_param()), one fp32 blob:
+ *   [0, P) parameters, [P, 2P) Adam's first moments, [2P, 3P) second moments, each in the engine's `flat` order;
+ *   [3P] = step mod 2^24, [3P + 1] = step div 2^24 (Adam's step counter, both exact in fp32).
+ *   _state_load rebuilds every pack _load rebuilds and does NOT reset the optimizer: the engine continues bit-identically. */
+#define LEMO_MASK_NONE 0
+#define LEMO_MASK_RANDOM 1
+#define LEMO_MASK_PROX 2
+typedef struct lemo_aetrain_epoch_desc {
+  const float* data;
+  int n_clips;
+  const int* idx;
+  int n_steps;
+  int recipe;
+  const int* marker_ids;
+  const float* masks;
+  int n_masks, mask_len;
+  const int* mask_idx;
+  float* log;
+  int train;
+} lemo_aetrain_epoch_desc;
+typedef struct lemo_sptrain_epoch_desc {
+  const float* data;
+  int n_clips;
+  const int* idx;
+  int n_steps;
+  float* log;
+  int train;
+} lemo_sptrain_epoch_desc;
+int lemo_aetrain_epoch(void* h, const lemo_aetrain_epoch_desc* d, void* stream);
+int lemo_aetrain_batch(void* h, const lemo_aetrain_epoch_desc* d, int step, float* x, float* y, void* stream);
+long long lemo_aetrain_state_floats(void);
+int lemo_aetrain_state_save(void* h, float* out, void* stream);
+int lemo_aetrain_state_load(void* h, const float* in, void* stream);
+int lemo_sptrain_epoch(void* h, const lemo_sptrain_epoch_desc* d, void* stream);
+int lemo_sptrain_batch(void* h, const lemo_sptrain_epoch_desc* d, int step, float* x, void* stream);
+long long lemo_sptrain_state_floats(void);
+int lemo_sptrain_state_save(void* h, float* out, void* stream);
+int lemo_sptrain_state_load(void* h, const float* in, void* stream);
+
 /* ---- stream capture helpers: record everything a host-side step enqueues on `stream` (HIP kernels of this library
  * and the caller's own device work alike) into an executable graph, replay it with one call.  Relaxed capture mode;
  * the caller guarantees that the step does not synchronise and that every buffer it touches outlives the replays. */

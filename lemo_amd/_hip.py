@@ -79,6 +79,20 @@ class AetrainDesc(C.Structure):
                 ('w_c', C.c_float), ('ws', vp), ('ws_floats', C.c_longlong), ('use_graph', C.c_int)]
 
 
+class AetrainEpochDesc(C.Structure):
+    """lemo_aetrain_epoch_desc"""
+    _fields_ = [('data', vp), ('n_clips', C.c_int), ('idx', vp), ('n_steps', C.c_int), ('recipe', C.c_int), ('marker_ids', vp),
+                ('masks', vp), ('n_masks', C.c_int), ('mask_len', C.c_int), ('mask_idx', vp), ('log', vp), ('train', C.c_int)]
+
+
+class SptrainEpochDesc(C.Structure):
+    """lemo_sptrain_epoch_desc"""
+    _fields_ = [('data', vp), ('n_clips', C.c_int), ('idx', vp), ('n_steps', C.c_int), ('log', vp), ('train', C.c_int)]
+
+
+MASK_NONE, MASK_RANDOM, MASK_PROX = 0, 1, 2
+
+
 class SkinConst(C.Structure):
     _fields_ = [('V', C.c_int), ('NC', C.c_int), ('KW', C.c_int), ('blend_fp32', C.c_int)] + \
         [(n, vp) for n in ('Dg', 'v_template', 'w_idx', 'w_val', 'DgH')] + [('dgh_inv', C.c_float)]
@@ -279,6 +293,16 @@ _SIGS = {
     'lemo_aetrain_params': (C.c_int, [vp, vp, vp]),
     'lemo_aetrain_grads': (C.c_int, [vp, vp, vp]),
     'lemo_aetrain_pool_winners': (C.c_int, [vp, C.c_int, vp, vp]),
+    'lemo_aetrain_epoch': (C.c_int, [vp, C.POINTER(AetrainEpochDesc), vp]),
+    'lemo_aetrain_batch': (C.c_int, [vp, C.POINTER(AetrainEpochDesc), C.c_int, vp, vp, vp]),
+    'lemo_aetrain_state_floats': (C.c_longlong, []),
+    'lemo_aetrain_state_save': (C.c_int, [vp, vp, vp]),
+    'lemo_aetrain_state_load': (C.c_int, [vp, vp, vp]),
+    'lemo_sptrain_epoch': (C.c_int, [vp, C.POINTER(SptrainEpochDesc), vp]),
+    'lemo_sptrain_batch': (C.c_int, [vp, C.POINTER(SptrainEpochDesc), C.c_int, vp, vp]),
+    'lemo_sptrain_state_floats': (C.c_longlong, []),
+    'lemo_sptrain_state_save': (C.c_int, [vp, vp, vp]),
+    'lemo_sptrain_state_load': (C.c_int, [vp, vp, vp]),
     'lemo_sdf_sample': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp]),
     'lemo_fit_create': (vp, [C.POINTER(FitDesc)]),
     'lemo_fit_destroy': (None, [vp]),

@@ -15,6 +15,7 @@
 //   * Adam + backward-pack rebuild: ae_adam_kernel, which sums those partials in (group, slab) order.
 // No float atomics: every sum has a fixed order, so a graph replay, an eager run and a second engine give identical bits.
 #include "ae_engine.hpp"
+#include "train_epoch.hpp"
 
 #include <cstring>
 #include <new>
@@ -268,6 +269,7 @@ struct AetEngine {
   unsigned char* idx[5];
   size_t cs = 0;
   hipGraphExec_t exec = nullptr;
+  hipGraphExec_t exec_ep[2] = {nullptr, nullptr};      // one step of an epoch (assemble, step, log): [0] evaluation, [1] training
 };
 
 static bool aet_shape_ok(int H, int W, int bs) {
@@ -447,6 +449,35 @@ static int aet_stage(AetEngine* e, const float* x, const float* y, hipStream_t s
   return (int)hipGetLastError();
 }
 
+// ---- the loop level: an epoch of different batches assembled on the device (train_epoch.hpp)
+static EpochBlock* aet_block(AetEngine* e) { return reinterpret_cast<EpochBlock*>(e->ctr + EP_BLOCK_OFF); }
+
+// the descriptor's shape rules (the index VALUES live on the device: the caller validates them, lemo_amd/infill_train.py does)
+static int aet_epoch_block(const AetEngine* e, const lemo_aetrain_epoch_desc* d, EpochBlock* B) {
+  if (!d || !d->data || !d->idx || d->n_clips < 1 || d->n_steps < 1) return LEMO_ERR_ARG;
+  const int dd = e->H[0] - 2, T = e->W[0] - 16;
+  if (T < 9) return LEMO_ERR_SHAPE;                                 // reflect padding by 8 needs more than 8 frames
+  if (d->recipe != LEMO_MASK_NONE && d->recipe != LEMO_MASK_RANDOM && d->recipe != LEMO_MASK_PROX) return LEMO_ERR_ARG;
+  if (d->recipe != LEMO_MASK_NONE && dd != 208) return LEMO_ERR_ARG;             // 3 pelvis + 3 x 67 marker + 4 contact rows
+  if (d->recipe == LEMO_MASK_RANDOM && !d->marker_ids) return LEMO_ERR_ARG;
+  if (d->recipe == LEMO_MASK_PROX && (!d->masks || !d->mask_idx || d->n_masks < 1 || d->mask_len < T)) return LEMO_ERR_ARG;
+  *B = EpochBlock{d->data, d->idx, d->marker_ids, d->masks, d->mask_idx, d->log, d->n_clips, d->n_masks, d->mask_len, d->n_steps,
+                  d->recipe, 0};
+  return 0;
+}
+
+// one step of an epoch: every kernel reads the step from the device-side cursor
+static int aet_epoch_step(AetEngine* e, bool train, hipStream_t s) {
+  CHK_(aet_assemble(EpochBlock{}, aet_block(e), 0, e->x8, e->cs, e->ybuf, e->bs, e->H[0], e->W[0], s));
+  if (train) {
+    CHK_(aet_train_step(e, s));
+  } else {
+    CHK_(aet_forward(e, s));
+    CHK_(aet_loss(e, false, s));
+  }
+  return ep_end(aet_block(e), e->losses, 4, s);
+}
+
 }  // namespace lemo
 
 using namespace lemo;
@@ -479,6 +510,7 @@ void lemo_aetrain_destroy(void* h) {
   AetEngine* e = (AetEngine*)h;
   if (!e) return;
   if (e->exec) (void)hipGraphExecDestroy(e->exec);
+  for (int k = 0; k < 2; ++k) if (e->exec_ep[k]) (void)hipGraphExecDestroy(e->exec_ep[k]);
   delete e;
 }
 
@@ -556,6 +588,67 @@ int lemo_aetrain_grads(void* h, float* flat_out, void* stream) {
   hipLaunchKernelGGL(aet_grad_kernel, dim3((A.n_all + 255) / 256), dim3(256), 0, s, A, e->gpk);
   CHK_((int)hipGetLastError());
   return ae_pack_launch(aet_pack_args(e), true, e->gpk, flat_out, nullptr, s);
+}
+
+int lemo_aetrain_epoch(void* h, const lemo_aetrain_epoch_desc* d, void* stream) {
+  AetEngine* e = (AetEngine*)h;
+  if (!e || !d || !d->log) return LEMO_ERR_ARG;
+  EpochBlock B;
+  CHK_(aet_epoch_block(e, d, &B));
+  if (!e->loaded) return LEMO_ERR_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const bool train = d->train != 0;
+  CHK_(ep_begin(B, aet_block(e), s));
+  if (e->use_graph) CHK_(capture_chain(&e->exec_ep[train], s, [&] { return aet_epoch_step(e, train, s); }));
+  for (int i = 0; i < d->n_steps; ++i) {
+    if (e->use_graph) CHK_((int)hipGraphLaunch(e->exec_ep[train], s));
+    else CHK_(aet_epoch_step(e, train, s));
+  }
+  return 0;
+}
+
+int lemo_aetrain_batch(void* h, const lemo_aetrain_epoch_desc* d, int step, float* x, float* y, void* stream) {
+  AetEngine* e = (AetEngine*)h;
+  if (!e || !x || !y) return LEMO_ERR_ARG;
+  EpochBlock B;
+  CHK_(aet_epoch_block(e, d, &B));
+  if (step < 0 || step >= d->n_steps) return LEMO_ERR_ARG;
+  return aet_assemble_api(B, step, x, y, e->bs, e->H[0], e->W[0], (hipStream_t)stream);
+}
+
+long long lemo_aetrain_state_floats(void) {
+  AetEngine e;
+  size_t total = 0;
+  aet_layout(&e, 8, 8, 1, nullptr, &total);
+  return 3ll * e.n_flat + 2;
+}
+
+int lemo_aetrain_state_save(void* h, float* out, void* stream) {
+  AetEngine* e = (AetEngine*)h;
+  if (!e || !out) return LEMO_ERR_ARG;
+  if (!e->loaded) return LEMO_ERR_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const AePackArgs P = aet_pack_args(e);
+  CHK_(ae_pack_launch(P, true, e->theta, out, nullptr, s));
+  CHK_(ae_pack_launch(P, true, e->m, out + e->n_flat, nullptr, s));
+  CHK_(ae_pack_launch(P, true, e->v, out + 2 * (size_t)e->n_flat, nullptr, s));
+  return train_step_counter(e->ctr, out + 3 * (size_t)e->n_flat, true, s);
+}
+
+int lemo_aetrain_state_load(void* h, const float* in, void* stream) {
+  AetEngine* e = (AetEngine*)h;
+  if (!e || !in) return LEMO_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const AePackArgs P = aet_pack_args(e);
+  // the moments take the parameters' packing; the backward pack it writes on the way goes to the gradient scratch (gpk holds
+  // n_w + n_b >= n_wb floats and is rewritten by every lemo_aetrain_grads), then the parameters' own backward pack to wb
+  CHK_(ae_pack_launch(P, false, in + e->n_flat, e->m, e->gpk, s));
+  CHK_(ae_pack_launch(P, false, in + 2 * (size_t)e->n_flat, e->v, e->gpk, s));
+  CHK_(ae_pack_launch(P, false, in, e->theta, e->wb, s));
+  CHK_((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
+  CHK_(train_step_counter(e->ctr, const_cast<float*>(in) + 3 * (size_t)e->n_flat, false, s));
+  e->loaded = 1;
+  return 0;
 }
 
 int lemo_aetrain_pool_winners(void* h, int block, unsigned char* out, void* stream) {

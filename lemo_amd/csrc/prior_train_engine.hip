@@ -11,6 +11,7 @@
 // i.e. 36 bs + 48 launches, captured once as a graph when use_graph is set.  The fp32 parameters, Adam moments and gradients
 // are one flat vector in the reference's state_dict order (Enc then Dec); layers 0 of Enc and 8, 9 of Dec read it directly.
 #include "kernels.hpp"
+#include "train_epoch.hpp"
 
 #include <cstring>
 #include <new>
@@ -38,6 +39,7 @@ struct SpEngine {
   int nl, nsp;                          // L1 partials (all images), smoothness partials per image
   SpPackJobs pk;
   hipGraphExec_t exec;
+  hipGraphExec_t exec_ep[2];            // one step of an epoch (assemble, step, log): [0] evaluation, [1] training
 };
 
 static int sp_layout(SpEngine* e, int H, int W, int bs, float* base, size_t* total) {
@@ -158,6 +160,22 @@ static int sp_run(SpEngine* e, hipStream_t s, bool train) {
   return sp_repack(e->pk, e->theta, s);
 }
 
+// ---- the loop level: an epoch of different batches assembled on the device (train_epoch.hpp)
+static EpochBlock* sp_block(SpEngine* e) { return reinterpret_cast<EpochBlock*>(e->ctr + EP_BLOCK_OFF); }
+
+static int sp_epoch_block(const SpEngine* e, const lemo_sptrain_epoch_desc* d, EpochBlock* B) {
+  if (!d || !d->data || !d->idx || d->n_clips < 1 || d->n_steps < 1) return LEMO_ERR_ARG;
+  if (e->W - 16 < 9 || e->H < 4) return LEMO_ERR_SHAPE;            // reflect padding by (8, 1) needs more than 8 velocity frames, 2 rows
+  *B = EpochBlock{d->data, d->idx, nullptr, nullptr, nullptr, d->log, d->n_clips, 0, 0, d->n_steps, LEMO_MASK_NONE, 0};
+  return 0;
+}
+
+static int sp_epoch_step(SpEngine* e, bool train, hipStream_t s) {
+  SP_CHK(sp_assemble(EpochBlock{}, sp_block(e), 0, e->xin, e->bs, e->H, e->W, s));
+  SP_CHK(sp_run(e, s, train));
+  return ep_end(sp_block(e), e->losses, 3, s);
+}
+
 }  // namespace lemo
 
 using namespace lemo;
@@ -197,6 +215,7 @@ void lemo_sptrain_destroy(void* h) {
   SpEngine* e = (SpEngine*)h;
   if (!e) return;
   if (e->exec) (void)hipGraphExecDestroy(e->exec);
+  for (int k = 0; k < 2; ++k) if (e->exec_ep[k]) (void)hipGraphExecDestroy(e->exec_ep[k]);
   delete e;
 }
 
@@ -268,6 +287,61 @@ int lemo_sptrain_grads(void* h, float* flat_out, void* stream) {
   if (!e || !flat_out) return LEMO_ERR_ARG;
   if (!e->loaded) return LEMO_ERR_STATE;
   return (int)hipMemcpyAsync(flat_out, e->grad, sizeof(float) * e->n_param, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+int lemo_sptrain_epoch(void* h, const lemo_sptrain_epoch_desc* d, void* stream) {
+  SpEngine* e = (SpEngine*)h;
+  if (!e || !d || !d->log) return LEMO_ERR_ARG;
+  EpochBlock B;
+  SP_CHK(sp_epoch_block(e, d, &B));
+  if (!e->loaded) return LEMO_ERR_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const bool train = d->train != 0;
+  SP_CHK(ep_begin(B, sp_block(e), s));
+  if (e->use_graph) SP_CHK(capture_chain(&e->exec_ep[train], s, [&] { return sp_epoch_step(e, train, s); }));
+  for (int i = 0; i < d->n_steps; ++i) {
+    if (e->use_graph) SP_CHK((int)hipGraphLaunch(e->exec_ep[train], s));
+    else SP_CHK(sp_epoch_step(e, train, s));
+  }
+  return 0;
+}
+
+int lemo_sptrain_batch(void* h, const lemo_sptrain_epoch_desc* d, int step, float* x, void* stream) {
+  SpEngine* e = (SpEngine*)h;
+  if (!e || !x) return LEMO_ERR_ARG;
+  EpochBlock B;
+  SP_CHK(sp_epoch_block(e, d, &B));
+  if (step < 0 || step >= d->n_steps) return LEMO_ERR_ARG;
+  return sp_assemble(B, nullptr, step, x, e->bs, e->H, e->W, (hipStream_t)stream);
+}
+
+long long lemo_sptrain_state_floats(void) { return 3ll * lemo_sptrain_n_param() + 2; }
+
+int lemo_sptrain_state_save(void* h, float* out, void* stream) {
+  SpEngine* e = (SpEngine*)h;
+  if (!e || !out) return LEMO_ERR_ARG;
+  if (!e->loaded) return LEMO_ERR_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)e->n_param;
+  SP_CHK((int)hipMemcpyAsync(out, e->theta, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  SP_CHK((int)hipMemcpyAsync(out + n, e->m, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  SP_CHK((int)hipMemcpyAsync(out + 2 * n, e->v, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  return train_step_counter(e->ctr, out + 3 * n, true, s);
+}
+
+int lemo_sptrain_state_load(void* h, const float* in, void* stream) {
+  SpEngine* e = (SpEngine*)h;
+  if (!e || !in) return LEMO_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)e->n_param;
+  SP_CHK((int)hipMemcpyAsync(e->theta, in, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  SP_CHK((int)hipMemcpyAsync(e->m, in + n, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  SP_CHK((int)hipMemcpyAsync(e->v, in + 2 * n, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  SP_CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
+  SP_CHK(train_step_counter(e->ctr, const_cast<float*>(in) + 3 * n, false, s));
+  SP_CHK(sp_repack(e->pk, e->theta, s));
+  e->loaded = 1;
+  return 0;
 }
 
 long long lemo_wgrad3x3_batched_ws_floats(int H, int W, int bs, int ca, int cb) {

@@ -235,6 +235,122 @@ class InfillPriorTrainer:
         """the parameters as CPU tensors under the reference's keys (enc_blc1.main.0.weight ... dec_blc5.deconv2.bias)"""
         return unflatten_state(self.flat_params())
 
+    # ---- the loop level: the dataset on the device, one call per epoch (lemo_aetrain_epoch)
+    def upload_dataset(self, clips) -> None:
+        """clips [N, 4, d, T] (d + 2 = H, T + 16 = W): the unpadded clip images the epochs gather their batches from"""
+        t = torch.as_tensor(np.asarray(clips) if not torch.is_tensor(clips) else clips)
+        if t.dim() != 4 or tuple(t.shape[1:]) != (4, self.H - 2, self.W - 16) or t.shape[0] < 1:
+            raise ValueError(f'expected clips [N, 4, {self.H - 2}, {self.W - 16}], got {tuple(t.shape)}')
+        if self.W - 16 < 9:
+            raise ValueError('reflect padding by 8 needs clips of more than 8 frames')
+        self._data = t.to(self.device, torch.float32).contiguous()
+
+    def upload_prox_masks(self, masks) -> None:
+        """the PROX marker masks (1 = visible): what ``load_prox_mask_clips`` returns, [M, L, 67 * 3] with each marker's column
+        repeated for its 3 rows, or [M, L, 67]; L >= T.  Kept on the device as [M, 67, L]."""
+        m = torch.as_tensor(np.asarray(masks) if not torch.is_tensor(masks) else masks).float()
+        if m.dim() != 3 or m.shape[0] < 1 or m.shape[2] not in (67, 201):
+            raise ValueError(f'expected masks [M, L, 201] or [M, L, 67], got {tuple(m.shape)}')
+        if m.shape[2] == 201:
+            m3 = m.reshape(m.shape[0], m.shape[1], 67, 3)
+            if not (torch.equal(m3[..., 0], m3[..., 1]) and torch.equal(m3[..., 0], m3[..., 2])):
+                raise ValueError("a marker's three mask columns differ: one mask per marker and frame is expected")
+            m = m3[..., 0]
+        if m.shape[1] < self.W - 16:
+            raise ValueError(f'mask clips of {m.shape[1]} frames are shorter than the clips ({self.W - 16} frames)')
+        self._masks = m.permute(0, 2, 1).contiguous().to(self.device)
+
+    def _index_table(self, t, name, lo, hi, tail=()):
+        t = torch.as_tensor(np.asarray(t) if not torch.is_tensor(t) else t)
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError(f'{name} must be an integer tensor')
+        t = t.cpu().long()
+        if t.dim() != 2 + len(tail) or t.shape[1] != self.bs or tuple(t.shape[2:]) != tuple(tail) or t.shape[0] < 1:
+            raise ValueError(f'{name}: expected [n_steps, {self.bs}{"".join(", %d" % v for v in tail)}], got {tuple(t.shape)}')
+        if int(t.min()) < lo or int(t.max()) >= hi:
+            raise ValueError(f'{name} holds values outside [{lo}, {hi})')
+        return t.to(torch.int32).contiguous()
+
+    def _epoch_desc(self, idx, marker_ids, mask_idx):
+        """validates every index on the host (nothing has been launched when it raises) -> (descriptor, the tensors it points into)"""
+        if getattr(self, '_data', None) is None:
+            raise ValueError('upload_dataset first')
+        if marker_ids is not None and mask_idx is not None:
+            raise ValueError('one masking recipe per call: marker_ids (random markers) or mask_idx (PROX masks)')
+        idx = self._index_table(idx, 'idx', 0, self._data.shape[0])
+        n_steps = idx.shape[0]
+        keep = [idx.to(self.device)]
+        d = _hip.AetrainEpochDesc(data=ptr(self._data), n_clips=int(self._data.shape[0]), idx=ptr(keep[0]), n_steps=n_steps,
+                                  recipe=_hip.MASK_NONE)
+        if marker_ids is not None or mask_idx is not None:
+            if self.H - 2 != 208:
+                raise ValueError(f'the masking recipes are defined for 67 markers (d = 208), the trainer has d = {self.H - 2}')
+        if marker_ids is not None:
+            ids = torch.as_tensor(np.asarray(marker_ids) if not torch.is_tensor(marker_ids) else marker_ids)
+            if ids.dim() == 3 and 1 <= ids.shape[2] < 6:                       # the reference draws 1 - 6 ids per step
+                ids = torch.cat([ids, ids.new_full(tuple(ids.shape[:2]) + (6 - ids.shape[2],), -1)], dim=2)
+            ids = self._index_table(ids, 'marker_ids', -1, 67, tail=(6,))
+            if ids.shape[0] != n_steps:
+                raise ValueError(f'marker_ids has {ids.shape[0]} steps, idx {n_steps}')
+            keep.append(ids.to(self.device))
+            d.recipe, d.marker_ids = _hip.MASK_RANDOM, ptr(keep[-1])
+        if mask_idx is not None:
+            if getattr(self, '_masks', None) is None:
+                raise ValueError('upload_prox_masks first')
+            mi = self._index_table(mask_idx, 'mask_idx', 0, self._masks.shape[0])
+            if mi.shape[0] != n_steps:
+                raise ValueError(f'mask_idx has {mi.shape[0]} steps, idx {n_steps}')
+            keep.append(mi.to(self.device))
+            d.recipe, d.masks, d.n_masks, d.mask_len, d.mask_idx = (_hip.MASK_PROX, ptr(self._masks), int(self._masks.shape[0]),
+                                                                    int(self._masks.shape[2]), ptr(keep[-1]))
+        return d, keep
+
+    def _epoch(self, idx, marker_ids, mask_idx, train):
+        d, keep = self._epoch_desc(idx, marker_ids, mask_idx)
+        log = torch.zeros(d.n_steps, 4, dtype=torch.float32, device=self.device)
+        d.log, d.train = ptr(log), int(train)
+        self._call(lambda s: self.lib.check(self.lib.aetrain_epoch(self.h, ctypes.byref(d), s), 'aetrain_epoch'))
+        out = log.cpu()                                                        # the epoch's one host wait (keeps `keep` alive until then)
+        del keep
+        return out
+
+    def fit_epoch(self, idx, marker_ids=None, mask_idx=None) -> torch.Tensor:
+        """one training step per row of idx [n_steps, bs] (clips of the uploaded dataset), masked by marker_ids [n_steps, bs, <= 6]
+        (random markers, -1 = unused slot) or mask_idx [n_steps, bs] (uploaded PROX masks) or not at all; the batches are
+        assembled on the device and the host does not wait between steps.  -> the loss log [n_steps, 4] on the CPU, rows
+        (loss_rec_body, loss_rec_body_v, loss_rec_contact_lbl, weighted total).  The RNG stays the caller's."""
+        return self._epoch(idx, marker_ids, mask_idx, True)
+
+    def evaluate_epoch(self, idx, marker_ids=None, mask_idx=None) -> torch.Tensor:
+        """the same batches and log under the current parameters, no update (the reference's test-loss loop; average the rows)"""
+        return self._epoch(idx, marker_ids, mask_idx, False)
+
+    def assemble(self, step: int, idx, marker_ids=None, mask_idx=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the batch of row `step` as the epoch kernels build it: (x [bs, 4, H, W], y [bs, H, W]) on the trainer's device"""
+        d, keep = self._epoch_desc(idx, marker_ids, mask_idx)
+        if not 0 <= int(step) < d.n_steps:
+            raise ValueError(f'step {step} outside [0, {d.n_steps})')
+        x = torch.empty(self.bs, 4, self.H, self.W, dtype=torch.float32, device=self.device)
+        y = torch.empty(self.bs, self.H, self.W, dtype=torch.float32, device=self.device)
+        self._call(lambda s: self.lib.check(self.lib.aetrain_batch(self.h, ctypes.byref(d), int(step), ptr(x), ptr(y), s), 'aetrain_batch'))
+        _hip.quiesce(self.device, self.lib)                                    # the index tables are released on return
+        return x, y
+
+    def save_state(self) -> torch.Tensor:
+        """parameters, both Adam moments and the step counter as one flat CPU tensor (include/lemo_hip.h has the layout)"""
+        out = torch.empty(int(self.lib.aetrain_state_floats()), dtype=torch.float32, device=self.device)
+        self._call(lambda s: self.lib.check(self.lib.aetrain_state_save(self.h, ptr(out), s), 'aetrain_state_save'))
+        return out.cpu()
+
+    def load_state(self, blob: torch.Tensor) -> None:
+        """restore what save_state returned: training continues bit-identically"""
+        n = int(self.lib.aetrain_state_floats())
+        if not torch.is_tensor(blob) or blob.dtype != torch.float32 or blob.dim() != 1 or blob.numel() != n:
+            raise ValueError(f'a training state is a flat float32 tensor of {n} values')
+        t = blob.to(self.device).contiguous()
+        self._call(lambda s: self.lib.check(self.lib.aetrain_state_load(self.h, ptr(t), s), 'aetrain_state_load'))
+        _hip.quiesce(self.device, self.lib)
+
     def close(self):
         if getattr(self, 'h', None):
             _hip.quiesce(self.device, self.lib)

@@ -155,6 +155,76 @@ class SmoothPriorTrainer:
         """(enc_sd, dec_sd) as CPU tensors under the reference's keys"""
         return unflatten_state(self.flat_params().numpy())
 
+    # ---- the loop level: the dataset on the device, one call per epoch (lemo_sptrain_epoch)
+    def upload_dataset(self, clips) -> None:
+        """clips [N, 1, d, T] (d + 2 = H, T + 15 = W): the clip images the epochs gather their batches from"""
+        t = torch.as_tensor(np.asarray(clips) if not torch.is_tensor(clips) else clips)
+        if t.dim() != 4 or tuple(t.shape[1:]) != (1, self.H - 2, self.W - 15) or t.shape[0] < 1:
+            raise ValueError(f'expected clips [N, 1, {self.H - 2}, {self.W - 15}], got {tuple(t.shape)}')
+        if self.W - 16 < 9 or self.H < 4:
+            raise ValueError('reflect padding by (8, 1) needs more than 8 velocity frames and 2 rows')
+        self._data = t.to(self.device, torch.float32).contiguous()
+
+    def _epoch_desc(self, idx):
+        """validates the indices on the host (nothing has been launched when it raises) -> (descriptor, the tensor it points into)"""
+        if getattr(self, '_data', None) is None:
+            raise ValueError('upload_dataset first')
+        t = torch.as_tensor(np.asarray(idx) if not torch.is_tensor(idx) else idx)
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise ValueError('idx must be an integer tensor')
+        t = t.cpu().long()
+        if t.dim() != 2 or t.shape[1] != self.bs or t.shape[0] < 1:
+            raise ValueError(f'idx: expected [n_steps, {self.bs}], got {tuple(t.shape)}')
+        if int(t.min()) < 0 or int(t.max()) >= self._data.shape[0]:
+            raise ValueError(f'idx holds values outside [0, {self._data.shape[0]})')
+        dev_idx = t.to(torch.int32).contiguous().to(self.device)
+        d = _hip.SptrainEpochDesc(data=ptr(self._data), n_clips=int(self._data.shape[0]), idx=ptr(dev_idx), n_steps=int(t.shape[0]))
+        return d, dev_idx
+
+    def _epoch(self, idx, train):
+        d, keep = self._epoch_desc(idx)
+        log = torch.zeros(d.n_steps, 3, dtype=torch.float32, device=self.device)
+        d.log, d.train = ptr(log), int(train)
+        self._call(lambda s: self.lib.check(self.lib.sptrain_epoch(self.h, ctypes.byref(d), s), 'sptrain_epoch'))
+        out = log.cpu()                                                        # the epoch's one host wait (keeps `keep` alive until then)
+        del keep
+        return out
+
+    def fit_epoch(self, idx) -> torch.Tensor:
+        """one training step per row of idx [n_steps, bs] (clips of the uploaded dataset): the batches are assembled on the device
+        and the host does not wait between steps.  -> the loss log [n_steps, 3] on the CPU, rows (loss_rec_v, loss_z_smooth,
+        weighted total).  The RNG (the permutation) stays the caller's."""
+        return self._epoch(idx, True)
+
+    def evaluate_epoch(self, idx) -> torch.Tensor:
+        """the same batches and log under the current parameters, no update"""
+        return self._epoch(idx, False)
+
+    def assemble(self, step: int, idx) -> torch.Tensor:
+        """the network input [bs, H, W] of row `step` as the epoch kernel builds it, on the trainer's device"""
+        d, keep = self._epoch_desc(idx)
+        if not 0 <= int(step) < d.n_steps:
+            raise ValueError(f'step {step} outside [0, {d.n_steps})')
+        x = torch.empty(self.bs, self.H, self.W, dtype=torch.float32, device=self.device)
+        self._call(lambda s: self.lib.check(self.lib.sptrain_batch(self.h, ctypes.byref(d), int(step), ptr(x), s), 'sptrain_batch'))
+        _hip.quiesce(self.device, self.lib)                                    # the index table is released on return
+        return x
+
+    def save_state(self) -> torch.Tensor:
+        """parameters, both Adam moments and the step counter as one flat CPU tensor (include/lemo_hip.h has the layout)"""
+        out = torch.empty(int(self.lib.sptrain_state_floats()), dtype=torch.float32, device=self.device)
+        self._call(lambda s: self.lib.check(self.lib.sptrain_state_save(self.h, ptr(out), s), 'sptrain_state_save'))
+        return out.cpu()
+
+    def load_state(self, blob: torch.Tensor) -> None:
+        """restore what save_state returned: training continues bit-identically"""
+        n = int(self.lib.sptrain_state_floats())
+        if not torch.is_tensor(blob) or blob.dtype != torch.float32 or blob.dim() != 1 or blob.numel() != n:
+            raise ValueError(f'a training state is a flat float32 tensor of {n} values')
+        t = blob.to(self.device).contiguous()
+        self._call(lambda s: self.lib.check(self.lib.sptrain_state_load(self.h, ptr(t), s), 'sptrain_state_load'))
+        _hip.quiesce(self.device, self.lib)
+
     def close(self):
         if getattr(self, 'h', None):
             _hip.quiesce(self.device, self.lib)
