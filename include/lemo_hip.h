@@ -274,6 +274,36 @@ int lemo_decode_clip(const float* rec, const float* traj, const double* stats, c
 int lemo_local_markers_4chan(const float* body, const float* contact, int T, int M1, float* image, double* rot_0_pivot,
                              void* stream);
 
+/* ---- clip images of the two priors from the markers of N clips (dataset_kernels.hip): what loader/train_loader_infill.py:134-330
+ * (mode 4CHAN) and loader/train_loader_smooth.py:130-204 (mode SMOOTH) do per clip on the host -- first-frame canonicalisation,
+ * contact labels, heading-normalised local representation, dataset statistics, normalisation.  One workgroup per clip;
+ * 2 <= T <= 256, 61 <= M <= 83 (LEMO_ERR_SHAPE otherwise).  d = 3 (M + 1) + 4 rows and F = T - 1 frames (4CHAN), d = 3 (M + 1)
+ * and F = T (SMOOTH).  fp32 through canonicalisation, labels and floor shift, float64 from there on, one rounding to fp32. */
+#define LEMO_CLIP_4CHAN 0
+#define LEMO_CLIP_SMOOTH 1
+typedef struct lemo_clip_repr_desc {
+  const float* markers;      /* [N][T][M][3] world frame */
+  const float* pelvis;       /* [N][T][3] joint 0 */
+  const float* hips0;        /* [N][2][3] joints 1 and 2 of frame 0 */
+  int n_clips, T, M, mode;
+  float fps;                 /* of the clips (contact speed threshold 0.22 m/s) */
+  int api_layout;            /* 0: image [N][C][d][F] (what the trainers' upload_dataset takes); 1: [N][C][F][d] (get_local_markers_4chan) */
+  const double* stats;       /* [2 d + 4] as lemo_decode_clip reads them, or NULL: unnormalised image.  SMOOTH: mean[d], std[d] (rows
+                                0-2 carry their own std and are the only ones normalised), std of all, std of rows 0-2, 0, 0 */
+  float* image;              /* write pass; C = 4 (4CHAN) or 1 (SMOOTH) */
+  double* rot_0_pivot;       /* [N] or NULL (4CHAN) */
+  float* contact;            /* [N][T][4] in {0, 1} or NULL (4CHAN, write pass) */
+  double* stats_part;        /* statistics pass: [N][lemo_clip_repr_stats_k()] per-clip partial sums */
+} lemo_clip_repr_desc;
+int lemo_clip_repr_stats_k(int M, int mode);
+/* per-clip partial sums of the unnormalised representation (d->stats is ignored) */
+int lemo_clip_repr_stats(const lemo_clip_repr_desc* d, void* stream);
+/* adds the partials of ALL n_clips clips in clip order (one workgroup; no atomics: the result does not depend on how the
+ * clips were split into lemo_clip_repr_stats launches) -> stats [2 d + 4], population standard deviations */
+int lemo_clip_repr_stats_reduce(const double* stats_part, int n_clips, int T, int M, int mode, double* stats, void* stream);
+/* recomputes the representation, normalises in float64 (d->stats) and stores the fp32 image, rot_0_pivot and contact */
+int lemo_clip_repr_write(const lemo_clip_repr_desc* d, void* stream);
+
 /* ---- motion-infilling autoencoder, models/AE.py:11-108 and its finetune step, opt_amass_temp.py:154-214 ----
  * (stride-1 convs / transposed convs run on lemo_conv3x3_mfma; these are the remaining layer types) */
 /* MaxPool2d(3,2,1): out is CG8P of ((H-1)/2+1) x ((W-1)/2+1); idx [C/8][Ho*Wo][8] winning tap (uint8) */

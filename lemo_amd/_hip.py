@@ -93,6 +93,16 @@ class SptrainEpochDesc(C.Structure):
 MASK_NONE, MASK_RANDOM, MASK_PROX = 0, 1, 2
 
 
+class ClipReprDesc(C.Structure):
+    """lemo_clip_repr_desc"""
+    _fields_ = [('markers', vp), ('pelvis', vp), ('hips0', vp), ('n_clips', C.c_int), ('T', C.c_int), ('M', C.c_int), ('mode', C.c_int),
+                ('fps', C.c_float), ('api_layout', C.c_int), ('stats', vp), ('image', vp), ('rot_0_pivot', vp), ('contact', vp),
+                ('stats_part', vp)]
+
+
+CLIP_4CHAN, CLIP_SMOOTH = 0, 1
+
+
 class SkinConst(C.Structure):
     _fields_ = [('V', C.c_int), ('NC', C.c_int), ('KW', C.c_int), ('blend_fp32', C.c_int)] + \
         [(n, vp) for n in ('Dg', 'v_template', 'w_idx', 'w_val', 'DgH')] + [('dgh_inv', C.c_float)]
@@ -212,6 +222,10 @@ _SIGS = {
     'lemo_reconstruct_global_body_dev': (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
     'lemo_local_markers_4chan': (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp]),
     'lemo_decode_clip': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]),
+    'lemo_clip_repr_stats_k': (C.c_int, [C.c_int, C.c_int]),
+    'lemo_clip_repr_stats': (C.c_int, [C.POINTER(ClipReprDesc), vp]),
+    'lemo_clip_repr_stats_reduce': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    'lemo_clip_repr_write': (C.c_int, [C.POINTER(ClipReprDesc), vp]),
     'lemo_conv3x3_split_supported': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     'lemo_conv3x3_mfma_split': (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     'lemo_conv3x3_mfma_split_census': (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
