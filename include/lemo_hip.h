@@ -281,6 +281,8 @@ int lemo_local_markers_4chan(const float* body, const float* contact, int T, int
  * and F = T (SMOOTH).  fp32 through canonicalisation, labels and floor shift, float64 from there on, one rounding to fp32. */
 #define LEMO_CLIP_4CHAN 0
 #define LEMO_CLIP_SMOOTH 1
+#define LEMO_CLIP_GLOBAL 2   /* train_loader_smooth.py mode global_markers: d = 3 M rows (M = 67 or 81; LEMO_ERR_SHAPE otherwise), F = T,
+                              * every row (p - marker 0 of frame 0) . R0 in fp32, all rows normalised, one scalar std */
 typedef struct lemo_clip_repr_desc {
   const float* markers;      /* [N][T][M][3] world frame */
   const float* pelvis;       /* [N][T][3] joint 0 */
@@ -290,7 +292,7 @@ typedef struct lemo_clip_repr_desc {
   int api_layout;            /* 0: image [N][C][d][F] (what the trainers' upload_dataset takes); 1: [N][C][F][d] (get_local_markers_4chan) */
   const double* stats;       /* [2 d + 4] as lemo_decode_clip reads them, or NULL: unnormalised image.  SMOOTH: mean[d], std[d] (rows
                                 0-2 carry their own std and are the only ones normalised), std of all, std of rows 0-2, 0, 0 */
-  float* image;              /* write pass; C = 4 (4CHAN) or 1 (SMOOTH) */
+  float* image;              /* write pass; C = 4 (4CHAN) or 1 (SMOOTH, GLOBAL) */
   double* rot_0_pivot;       /* [N] or NULL (4CHAN) */
   float* contact;            /* [N][T][4] in {0, 1} or NULL (4CHAN, write pass) */
   double* stats_part;        /* statistics pass: [N][lemo_clip_repr_stats_k()] per-clip partial sums */

@@ -100,7 +100,7 @@ class ClipReprDesc(C.Structure):
                 ('stats_part', vp)]
 
 
-CLIP_4CHAN, CLIP_SMOOTH = 0, 1
+CLIP_4CHAN, CLIP_SMOOTH, CLIP_GLOBAL = 0, 1, 2
 
 
 class SkinConst(C.Structure):

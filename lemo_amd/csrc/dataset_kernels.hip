@@ -2,6 +2,7 @@
 // loaders do per clip on the host,
 //     loader/train_loader_infill.py:134-277   mode local_markers_4chan -> [4][d][T-1], d = 3 (1 + M) + 4
 //     loader/train_loader_smooth.py:130-176   mode local_markers       -> [1][d][T],   d = 3 (1 + M)
+//     loader/train_loader_smooth.py:130-167   mode global_markers      -> [1][d][T],   d = 3 M  (what the shipped smoothness prior reads)
 // followed by their dataset-wide statistics and normalisation (:281-330 / :180-204).  One workgroup per clip (T <= 256
 // frames, like marker_kernels.hip).  The representation is computed by ONE device function, ds_value, after ds_prepare has
 // left the clip's per-frame state in LDS; the statistics pass, the write pass and the [T][d] (API-layout) variant of the
@@ -36,7 +37,12 @@ struct ClipCtx {
   unsigned char lbl[DS_T];                                   // 4 contact bits per frame
 };
 
-__device__ __forceinline__ int ds_rows(const lemo_clip_repr_desc& D) { return 3 * (D.M + 1) + (D.mode == LEMO_CLIP_4CHAN ? 4 : 0); }
+__host__ __device__ __forceinline__ int ds_rows_of(int M, int mode) {
+  return mode == LEMO_CLIP_GLOBAL ? 3 * M : 3 * (M + 1) + (mode == LEMO_CLIP_4CHAN ? 4 : 0);
+}
+__device__ __forceinline__ int ds_rows(const lemo_clip_repr_desc& D) { return ds_rows_of(D.M, D.mode); }
+// body slots of three rows each: pelvis + markers, or (global_markers) the markers alone
+__device__ __forceinline__ int ds_slots(const lemo_clip_repr_desc& D) { return D.mode == LEMO_CLIP_GLOBAL ? D.M : D.M + 1; }
 __device__ __forceinline__ int ds_frames(const lemo_clip_repr_desc& D) { return D.mode == LEMO_CLIP_4CHAN ? D.T - 1 : D.T; }
 
 // (p - org) . R0 in fp32; the up column of R0 is (0, 0, 1)
@@ -163,9 +169,14 @@ __device__ void ds_prepare(const lemo_clip_repr_desc& D, int n, ClipCtx& c) {
   __syncthreads();
 }
 
-// The three rows of body slot j (0 = pelvis, 1 + m = marker m) at frame i, unnormalised.
+// The three rows of body slot j (0 = pelvis, 1 + m = marker m; global_markers: j = marker j, no pelvis) at frame i, unnormalised.
 __device__ __forceinline__ void ds_body(const lemo_clip_repr_desc& D, int n, const ClipCtx& c, int j, int i, double v[3]) {
   float px, py, pz, x, y, z;
+  if (D.mode == LEMO_CLIP_GLOBAL) {                          // (p - marker 0 of frame 0) . R0, fp32 (train_loader_smooth.py:143, 165)
+    ds_canon(c, ds_marker(D, n, i, j), c.morg, x, y, z);
+    v[0] = x; v[1] = y; v[2] = z;
+    return;
+  }
   ds_canon(c, ds_pelvis(D, n, i), c.org, px, py, pz);
   if (j == 0) { x = px; y = py; z = pz; }
   else ds_canon(c, ds_marker(D, n, i, j - 1), c.morg, x, y, z);
@@ -186,24 +197,24 @@ __device__ __forceinline__ double ds_value(const lemo_clip_repr_desc& D, int n, 
   if (ch == 1) return c.a[i];
   if (ch == 2) return c.b[i];
   if (ch == 3) return c.g[i];
-  const int nb = 3 * (D.M + 1);
+  const int nb = 3 * ds_slots(D);
   if (r >= nb) return (double)((c.lbl[i] >> (r - nb)) & 1);
   double v[3];
   ds_body(D, n, c, r / 3, i, v);
   return v[r % 3];
 }
 
-// stats [2 d + 4]: mean[d], std[d], then (4chan) mean / std of channels 1-2 and of channel 3.  The smoothness prior
-// normalises rows 0-2 only (train_loader_smooth.py:200).
+// stats [2 d + 4]: mean[d], std[d], then (4chan) mean / std of channels 1-2 and of channel 3.  local_markers normalises
+// rows 0-2 only (train_loader_smooth.py:200), global_markers every row (:191).
 __device__ __forceinline__ float ds_norm(const lemo_clip_repr_desc& D, int d, int ch, int r, double v) {
   const double* s = D.stats;
   if (!s) return (float)v;
-  if (ch == 0) return (D.mode == LEMO_CLIP_4CHAN || r < 3) ? (float)((v - s[r]) / s[d + r]) : (float)v;
+  if (ch == 0) return (D.mode != LEMO_CLIP_SMOOTH || r < 3) ? (float)((v - s[r]) / s[d + r]) : (float)v;
   return ch < 3 ? (float)((v - s[2 * d]) / s[2 * d + 1]) : (float)((v - s[2 * d + 2]) / s[2 * d + 3]);
 }
 
 // partials of clip n: part[r < d] = sum over frames of row r of channel 0, then
-//   [d + 0] sum of squares of channel 0     [d + 1] ... of its rows 0-2
+//   [d + 0] sum of squares of channel 0     [d + 1] ... of its rows 0-2 (global_markers: the sum of channel 0)
 //   [d + 2], [d + 3] sum, sum of squares of channels 1-2     [d + 4], [d + 5] of channel 3
 __global__ void __launch_bounds__(DS_T) ds_stats_kernel(lemo_clip_repr_desc D) {
   __shared__ ClipCtx c;
@@ -221,11 +232,15 @@ __global__ void __launch_bounds__(DS_T) ds_stats_kernel(lemo_clip_repr_desc D) {
       g[2] += c.g[i]; g[3] += c.g[i] * c.g[i];
     }
   __syncthreads();
-  if (t < d) { part[t] = s; c.a[t] = ss; }
+  if (t < d) { part[t] = s; c.a[t] = ss; c.b[t] = s; }
   __syncthreads();
   if (t == 0) {
     double all = 0.0, head = 0.0;
     for (int r = 0; r < d; ++r) { all += c.a[r]; if (r == 2) head = all; }
+    if (D.mode == LEMO_CLIP_GLOBAL) {
+      head = 0.0;
+      for (int r = 0; r < d; ++r) head += c.b[r];
+    }
     part[d] = all; part[d + 1] = head;
     for (int k = 0; k < 4; ++k) part[d + 2 + k] = g[k];
     part[d + 6] = 0.0; part[d + 7] = 0.0;
@@ -234,7 +249,7 @@ __global__ void __launch_bounds__(DS_T) ds_stats_kernel(lemo_clip_repr_desc D) {
 
 __global__ void __launch_bounds__(DS_T) ds_stats_reduce_kernel(const double* __restrict__ part, int N, int T, int M, int mode, double* __restrict__ stats) {
   __shared__ double tot[DS_T + DS_KPAD];
-  const int t = threadIdx.x, d = 3 * (M + 1) + (mode == LEMO_CLIP_4CHAN ? 4 : 0), K = d + DS_KPAD;
+  const int t = threadIdx.x, d = ds_rows_of(M, mode), K = d + DS_KPAD;
   for (int k = t; k < K; k += DS_T) {
     double s = 0.0;
     for (int n = 0; n < N; ++n) s += part[(size_t)n * K + k];       // clip order: independent of the launches that wrote them
@@ -246,7 +261,11 @@ __global__ void __launch_bounds__(DS_T) ds_stats_reduce_kernel(const double* __r
   for (int r = 0; r < d; ++r) { sum += tot[r]; if (r == 2) head = sum; }
   const double m_all = sum / (cnt * d), sd_all = sqrt(fmax(0.0, tot[d] / (cnt * d) - m_all * m_all));      // fmax: rounding must not make a variance negative
   const double m_head = head / (cnt * 3), sd_head = sqrt(fmax(0.0, tot[d + 1] / (cnt * 3) - m_head * m_head));
-  if (mode == LEMO_CLIP_4CHAN) {
+  if (mode == LEMO_CLIP_GLOBAL) {                            // one scalar std of the whole array, broadcast (train_loader_smooth.py:185)
+    const double m_tot = tot[d + 1] / (cnt * d), sd_tot = sqrt(fmax(0.0, tot[d] / (cnt * d) - m_tot * m_tot));
+    if (t < d) { stats[t] = tot[t] / cnt; stats[d + t] = sd_tot; }
+    if (t == 0) { stats[2 * d] = sd_tot; stats[2 * d + 1] = sd_tot; stats[2 * d + 2] = 0.0; stats[2 * d + 3] = 0.0; }
+  } else if (mode == LEMO_CLIP_4CHAN) {
     if (t < d) { stats[t] = t < d - 4 ? tot[t] / cnt : 0.0; stats[d + t] = t < d - 4 ? sd_all : 1.0; }
     if (t == 0) {
       const double mxy = tot[d + 2] / (2 * cnt), mr = tot[d + 4] / cnt;
@@ -266,7 +285,7 @@ __global__ void __launch_bounds__(DS_T) ds_write_kernel(lemo_clip_repr_desc D) {
   __shared__ ClipCtx c;
   __shared__ float vn[3][DS_T];
   const int n = blockIdx.x, t = threadIdx.x, d = ds_rows(D), F = ds_frames(D), M = D.M;
-  const int wave = t >> 6, lane = t & 63, NW = DS_T / 64;
+  const int wave = t >> 6, lane = t & 63, NW = DS_T / 64, nslot = ds_slots(D);
   const bool four = D.mode == LEMO_CLIP_4CHAN;
   ds_prepare(D, n, c);
   float* img = D.image + (size_t)n * (four ? 4 : 1) * d * F;
@@ -286,7 +305,7 @@ __global__ void __launch_bounds__(DS_T) ds_write_kernel(lemo_clip_repr_desc D) {
       }
     return;
   }
-  for (int j = wave; j <= M; j += NW)
+  for (int j = wave; j < nslot; j += NW)
     for (int i = lane; i < F; i += 64) {
       double v[3];
       ds_body(D, n, c, j, i, v);
@@ -303,12 +322,17 @@ __global__ void __launch_bounds__(DS_T) ds_write_kernel(lemo_clip_repr_desc D) {
   }
 }
 
+static int ds_check_shape(int n_clips, int T, int M, int mode) {
+  // foot markers 16 / 47 / 30 / 60 and direction markers 26 / 27 / 56 / 57; the statistics pass runs one thread per row
+  if (n_clips < 1 || T < 2 || T > DS_T || M < 61 || 3 * (M + 1) + 4 > DS_T) return LEMO_ERR_SHAPE;
+  if (mode == LEMO_CLIP_GLOBAL && M != 67 && M != 81) return LEMO_ERR_SHAPE;      // the two marker sets of the smoothness loader
+  return 0;
+}
+
 static int ds_check(const lemo_clip_repr_desc* D) {
   if (!D || !D->markers || !D->pelvis || !D->hips0) return LEMO_ERR_ARG;
-  if (D->mode != LEMO_CLIP_4CHAN && D->mode != LEMO_CLIP_SMOOTH) return LEMO_ERR_ARG;
-  // foot markers 16 / 47 / 30 / 60 and direction markers 26 / 27 / 56 / 57; the statistics pass runs one thread per row
-  if (D->n_clips < 1 || D->T < 2 || D->T > DS_T || D->M < 61 || 3 * (D->M + 1) + 4 > DS_T) return LEMO_ERR_SHAPE;
-  return 0;
+  if (D->mode < LEMO_CLIP_4CHAN || D->mode > LEMO_CLIP_GLOBAL) return LEMO_ERR_ARG;
+  return ds_check_shape(D->n_clips, D->T, D->M, D->mode);
 }
 
 int clip_repr_stats(const lemo_clip_repr_desc* D, hipStream_t s) {
@@ -319,8 +343,8 @@ int clip_repr_stats(const lemo_clip_repr_desc* D, hipStream_t s) {
 }
 
 int clip_repr_stats_reduce(const double* part, int n_clips, int T, int M, int mode, double* stats, hipStream_t s) {
-  if (!part || !stats || (mode != LEMO_CLIP_4CHAN && mode != LEMO_CLIP_SMOOTH)) return LEMO_ERR_ARG;
-  if (n_clips < 1 || T < 2 || T > DS_T || M < 61 || 3 * (M + 1) + 4 > DS_T) return LEMO_ERR_SHAPE;
+  if (!part || !stats || mode < LEMO_CLIP_4CHAN || mode > LEMO_CLIP_GLOBAL) return LEMO_ERR_ARG;
+  if (int e = ds_check_shape(n_clips, T, M, mode)) return e;
   hipLaunchKernelGGL(ds_stats_reduce_kernel, dim3(1), dim3(DS_T), 0, s, part, n_clips, T, M, mode, stats);
   return (int)hipGetLastError();
 }
@@ -336,7 +360,7 @@ int clip_repr_write(const lemo_clip_repr_desc* D, hipStream_t s) {
 }  // namespace lemo
 
 extern "C" {
-int lemo_clip_repr_stats_k(int M, int mode) { return 3 * (M + 1) + (mode == LEMO_CLIP_4CHAN ? 4 : 0) + DS_KPAD; }
+int lemo_clip_repr_stats_k(int M, int mode) { return lemo::ds_rows_of(M, mode) + DS_KPAD; }
 int lemo_clip_repr_stats(const lemo_clip_repr_desc* d, void* stream) { return lemo::clip_repr_stats(d, (hipStream_t)stream); }
 int lemo_clip_repr_stats_reduce(const double* stats_part, int n_clips, int T, int M, int mode, double* stats, void* stream) {
   return lemo::clip_repr_stats_reduce(stats_part, n_clips, T, M, mode, stats, (hipStream_t)stream);

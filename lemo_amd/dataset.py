@@ -15,6 +15,19 @@ only (the active-vertex path of the fitting engine), ``chunk`` clips per call; e
 (``'local_markers_4chan'``) / ``SmoothPriorTrainer.upload_dataset`` (``'local_markers'``: [N, 1, d, T]) take, and stays on
 the device; ``info['rot_0_pivot']`` and ``info['contact']`` are what ``loader/optimize_loader_amass_new.py`` hands the
 fitting side.
+
+The smoothness prior every fit uses was trained on a third representation, the smoothness loader's default
+``global_markers`` (``train_loader_smooth.py:164-167, 184-194``): the markers alone, relative to marker 0 of frame 0 in the
+first frame's heading, d = 3 M rows (243 with hands), every row normalised with the set's own mean and one scalar standard
+deviation -- the image the fit loop feeds ``Enc`` (``opt_amass_temp.py:366-380``).  ``local_markers`` is NOT that image.
+
+    builder = SmoothClipImageBuilder({'male': m, 'female': f}, with_hand=True)   # body_mode='global_markers'
+    images, info = builder.build(clips)                                       # [N, 1, 3 M, T] on the device
+    SmoothPriorTrainer(enc, dec, H=3 * 81 + 2, W=T - 1 + 16).upload_dataset(images)
+    save_stats(path, info['stats'])                                           # Xmean (1, 1, d) float32, Xstd (d,) float64
+
+``info['stats']`` is what ``AmassTemporalFitter(enc_state, Xmean, Xstd, ...)`` takes, so a prior retrained on someone's own
+AMASS split runs in the fit loop with that split's statistics.
 """
 from __future__ import annotations
 
@@ -83,10 +96,12 @@ class ClipImageBuilder:
     """``models``: ``lemo_amd`` SMPL-X modules per gender, created with ``use_pca=False, flat_hand_mean=True`` like the
     reference's loaders do."""
 
+    _MODES = MODES
+
     def __init__(self, models: Dict[str, object], mode: str = 'local_markers_4chan', with_hand: bool = False, clip_fps: int = 30,
                  chunk: int = 256, device=None, _lib: Optional[_hip.HipLib] = None):
-        if mode not in MODES:
-            raise ValueError(f'mode must be one of {sorted(MODES)}, got {mode!r}')
+        if mode not in self._MODES:
+            raise ValueError(f'mode must be one of {sorted(self._MODES)}, got {mode!r}')
         if not models or any(g not in ('male', 'female', 'neutral') for g in models):
             raise ValueError("models: {'male': ..., 'female': ...}")
         if int(chunk) < 1:
@@ -102,7 +117,11 @@ class ClipImageBuilder:
             if int(self.marker_ids.max()) >= m.data.V:
                 raise ValueError(f'the {g} model has {m.data.V} vertices, the marker set reaches vertex {int(self.marker_ids.max())}')
         self.M = len(self.marker_ids)
-        self.d = 3 * (self.M + 1) + (4 if mode == 'local_markers_4chan' else 0)
+        self._mode_id = self._MODES[mode]
+        self.d = self._rows()
+
+    def _rows(self) -> int:
+        return 3 * (self.M + 1) + (4 if self.mode == 'local_markers_4chan' else 0)
 
     # ---- host-side validation: nothing is launched before it has passed -------------------------------------------------------
     def _validate(self, clips) -> int:
@@ -198,7 +217,7 @@ class ClipImageBuilder:
     # ---- the native chain on markers that are already there (also the tests' way in) ----------------------------------------
     def _desc(self, markers, pelvis, hips0, lo, hi, **kw):
         return _hip.ClipReprDesc(markers=ptr(markers[lo:hi]), pelvis=ptr(pelvis[lo:hi]), hips0=ptr(hips0[lo:hi]), n_clips=hi - lo,
-                                 T=markers.shape[1], M=self.M, mode=MODES[self.mode], fps=self.clip_fps, **kw)
+                                 T=markers.shape[1], M=self.M, mode=self._mode_id, fps=self.clip_fps, **kw)
 
     def _check_markers(self, markers, pelvis, hips0):
         if markers.dim() != 4 or markers.shape[2:] != (self.M, 3) or markers.shape[0] < 1:
@@ -216,14 +235,14 @@ class ClipImageBuilder:
         markers, pelvis, hips0 = self._check_markers(markers, pelvis, hips0)
         lib, N, T = self.lib, markers.shape[0], markers.shape[1]
         s = lib.stream(self.device)
-        K = lib.clip_repr_stats_k(self.M, MODES[self.mode])
+        K = lib.clip_repr_stats_k(self.M, self._mode_id)
         part = torch.empty(N, K, dtype=torch.float64, device=self.device)
         for lo in range(0, N, self.chunk):
             hi = min(N, lo + self.chunk)
             d = self._desc(markers, pelvis, hips0, lo, hi, stats_part=ptr(part[lo:hi]))
             lib.check(lib.clip_repr_stats(C.byref(d), s), 'clip_repr_stats')
         out = torch.empty(2 * self.d + 4, dtype=torch.float64, device=self.device)
-        lib.check(lib.clip_repr_stats_reduce(ptr(part), N, T, self.M, MODES[self.mode], ptr(out), s), 'clip_repr_stats_reduce')
+        lib.check(lib.clip_repr_stats_reduce(ptr(part), N, T, self.M, self._mode_id, ptr(out), s), 'clip_repr_stats_reduce')
         return out
 
     def images_from_markers(self, markers, pelvis, hips0, stats_vec: Optional[torch.Tensor] = None, api_layout: bool = False):
@@ -252,17 +271,73 @@ class ClipImageBuilder:
         T = self._validate(clips)
         return self._stats_dict(self.stats_from_markers(*self._markers(clips, T)))
 
-    def build(self, clips, stats: Optional[Dict] = None, normalize: bool = True):
+    def _saved(self, vec: torch.Tensor) -> torch.Tensor:
+        """the statistics vector as the images are normalised with it: what ``_stats_dict`` hands out"""
+        return vec
+
+    def build(self, clips, stats: Optional[Dict] = None, normalize: bool = True, api_layout: bool = False):
         """-> (images, info).  ``stats=None`` is the reference's train split (statistics of these clips, then normalisation);
-        passing statistics is its test split; ``normalize=False`` gives the unnormalised images."""
+        passing statistics is its test split; ``normalize=False`` gives the unnormalised images; ``api_layout=True`` gives
+        [N, C, F, d] (frame-major rows) instead of the trainers' [N, C, d, F]."""
         T = self._validate(clips)
         vec = self._stats_vector(stats) if (stats is not None and normalize) else None
         markers, pelvis, hips0 = self._markers(clips, T)
         if normalize and vec is None:
-            vec = self.stats_from_markers(markers, pelvis, hips0)
-        img, piv, con = self.images_from_markers(markers, pelvis, hips0, vec if normalize else None)
+            vec = self._saved(self.stats_from_markers(markers, pelvis, hips0))
+        img, piv, con = self.images_from_markers(markers, pelvis, hips0, vec if normalize else None, api_layout=api_layout)
         info = dict(stats=self._stats_dict(vec) if vec is not None else None, rot_0_pivot=piv, contact=con)
         return img, info
 
     save_stats = staticmethod(save_stats)
     load_stats = staticmethod(load_stats)
+
+
+SMOOTH_BODY_MODES = {'global_markers': _hip.CLIP_GLOBAL}
+
+
+class SmoothClipImageBuilder(ClipImageBuilder):
+    """The smoothness prior's own training set, ``train_loader_smooth.py``'s default ``--body_mode global_markers``: images
+    [N, 1, 3 M, T] (M = 67, or 81 ``with_hand``), every row ``(p - marker 0 of frame 0) . R0`` of a marker coordinate,
+    normalised with the per-row mean and ONE standard deviation of the whole set.  Chunking, gender mixing, the active-vertex
+    forward and the validation are ``ClipImageBuilder``'s; statistics carry the reference's keys, shapes and dtypes
+    (``Xmean`` (1, 1, d) float32, ``Xstd`` (d,) float64), and the images are normalised with exactly those (the float32
+    ``Xmean``), so that ``build(clips, stats=info['stats'])`` repeats ``build(clips)`` bit for bit."""
+
+    _MODES = SMOOTH_BODY_MODES
+
+    def __init__(self, models: Dict[str, object], with_hand: bool = True, body_mode: str = 'global_markers', clip_fps: int = 30,
+                 chunk: int = 256, device=None, _lib: Optional[_hip.HipLib] = None):
+        if body_mode in ('global_joints', 'local_joints'):
+            raise ValueError(f'body_mode {body_mode!r} is not built here: the joint representations need all 55 regressed joints of '
+                             f'every frame, i.e. the all-vertex SMPL-X forward, and no shipped prior was trained on them')
+        if body_mode in MODES:
+            raise ValueError(f'body_mode {body_mode!r} is ClipImageBuilder(mode={body_mode!r})')
+        super().__init__(models, mode=body_mode, with_hand=with_hand, clip_fps=clip_fps, chunk=chunk, device=device, _lib=_lib)
+
+    def _rows(self) -> int:
+        return 3 * self.M
+
+    def _stats_vector(self, stats) -> torch.Tensor:
+        d = self.d
+        try:
+            mean, std = np.asarray(stats['Xmean'], np.float64).reshape(-1), np.asarray(stats['Xstd'], np.float64).reshape(-1)
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError(f'statistics do not fit mode {self.mode!r}: {e!r}') from None
+        if mean.shape != (d,) or std.shape != (d,):
+            raise ValueError(f'statistics do not fit mode {self.mode!r} with d = {d}: Xmean has {mean.size} entries, Xstd {std.size}')
+        v = np.zeros(2 * d + 4, np.float64)
+        v[:d], v[d:2 * d], v[2 * d], v[2 * d + 1] = mean, std, std[0], std[0]
+        return torch.from_numpy(v).to(self.device)
+
+    def _stats_dict(self, vec: torch.Tensor) -> Dict[str, np.ndarray]:
+        v, d = vec.cpu().numpy(), self.d
+        return dict(Xmean=v[:d].reshape(1, 1, d).astype(np.float32), Xstd=v[d:2 * d].copy())
+
+    def _saved(self, vec: torch.Tensor) -> torch.Tensor:
+        return self._stats_vector(self._stats_dict(vec))
+
+    def build(self, clips, stats: Optional[Dict] = None, normalize: bool = True, api_layout: bool = False):
+        """-> (images [N, 1, 3 M, T], info); ``api_layout=True``: [N, T, 3 M], the frame-major rows the fit loop feeds the
+        encoder.  ``info['rot_0_pivot']`` and ``info['contact']`` are None: this representation has neither."""
+        img, info = super().build(clips, stats=stats, normalize=normalize, api_layout=api_layout)
+        return (img[:, 0] if api_layout else img), info
