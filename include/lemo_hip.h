@@ -798,6 +798,32 @@ typedef struct lemo_prox_state {
 int lemo_prox_load_state(void* h, const lemo_prox_state* st, void* stream);
 int lemo_prox_save_state(void* h, const lemo_prox_state* st, void* stream);
 
+/* ---- occlusion masks (csrc/occlusion_kernels.hip): utils/get_occlusion_mask.py:111-147, 170-201 ----
+ * Pinhole camera in camera space (y down, z forward): u = fx X / Z + cx, v = fy Y / Z + cy; pixel [y][x] samples the ray through
+ * (x + 0.5, y + 0.5).  Depth is the camera-space Z of the nearest hit with znear <= Z <= zfar, 0 where nothing is hit.
+ * cull_backface: draw a triangle only if ((v1 - v0) x (v2 - v0)) . v0 < 0 (counter-clockwise as the camera sees it).
+ * LEMO_ERR_SHAPE: W or H outside [1, 32768], V / F / T / P < 1, P > 128, T > 65535; LEMO_ERR_ARG: null pointers, intrinsics or
+ * depth range that are not positive and finite.  Faces that name a vertex outside [0, V) are skipped. */
+typedef struct lemo_occl_cam {
+  float fx, fy, cx, cy;
+  float znear, zfar;              /* pyrender's defaults: 0.05, 100 */
+  int W, H;
+  int cull_backface;
+} lemo_occl_cam;
+/* verts [V][3], faces [F][3] (device); xf: host [12], a rigid transform [R | t] row-major applied to every vertex on load, or NULL;
+ * depth [H][W] (device) out.  Order-independent: the same mesh gives the same bits whatever the order of its faces. */
+int lemo_depth_raster(const float* verts, int V, const int* faces, int F, const float* xf, const lemo_occl_cam* cam, float* depth,
+                      void* stream);
+/* verts [T][V][3] (camera space), faces [F][3], points [T][P][3]: the body's depth at the pixel each point projects to (fx = proj_fx,
+ * fy = proj_fy, the centre of cam; truncated toward zero like astype(int)), without rendering the body, and the reference's rule
+ *   occluded <=> 0 <= x < W and 0 <= y < H and depth_scene[y][x] != 0 and depth_body - depth_scene[y][x] > thresh.
+ * depth_scene [H][W] as lemo_depth_raster wrote it for cam; ws [T][P] scratch; mask [T][P] out, 1 = visible; optional outputs (or
+ * NULL) depth_body [T][P] (0: the body does not cover the pixel, or the point is outside the image) and pix [T][P][2] = (x, y),
+ * INT_MIN where the projection is not finite. */
+int lemo_occlusion_query(const float* verts, int T, int V, const int* faces, int F, const float* points, int P, const lemo_occl_cam* cam,
+                         float proj_fx, float proj_fy, const float* depth_scene, float thresh, unsigned* ws, float* mask,
+                         float* depth_body, int* pix, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

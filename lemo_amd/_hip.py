@@ -103,6 +103,12 @@ class ClipReprDesc(C.Structure):
 CLIP_4CHAN, CLIP_SMOOTH, CLIP_GLOBAL = 0, 1, 2
 
 
+class OcclCam(C.Structure):
+    """lemo_occl_cam"""
+    _fields_ = [('fx', C.c_float), ('fy', C.c_float), ('cx', C.c_float), ('cy', C.c_float), ('znear', C.c_float), ('zfar', C.c_float),
+                ('W', C.c_int), ('H', C.c_int), ('cull_backface', C.c_int)]
+
+
 class SkinConst(C.Structure):
     _fields_ = [('V', C.c_int), ('NC', C.c_int), ('KW', C.c_int), ('blend_fp32', C.c_int)] + \
         [(n, vp) for n in ('Dg', 'v_template', 'w_idx', 'w_val', 'DgH')] + [('dgh_inv', C.c_float)]
@@ -333,6 +339,9 @@ _SIGS = {
     'lemo_prox_destroy': (None, [vp]),
     'lemo_prox_closure': (C.c_int, [vp, vp]),
     'lemo_prox_step': (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    'lemo_depth_raster': (C.c_int, [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(OcclCam), vp, vp]),
+    'lemo_occlusion_query': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(OcclCam), C.c_float, C.c_float, vp, C.c_float,
+                                       vp, vp, vp, vp, vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

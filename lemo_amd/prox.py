@@ -382,9 +382,15 @@ class ProxWindowEngine(_hip.StreamOrdered):
         jw = joint_weights_for(B, w, dev)
         T_['w2'] = ((jw * tf(joints_conf)) ** 2).contiguous()
         T_['gt'] = tf(gt_joints)
-        self.use_infill = body_markers_rec is not None and bool(np.asarray(marker_mask).size > np.asarray(marker_mask).sum())
+        if isinstance(marker_mask, torch.Tensor):                # a device mask (lemo_amd.occlusion.OcclusionMasker.markers) stays there
+            marker_mask = marker_mask.detach().to(dev, torch.float32).contiguous()
+            any_masked = lambda: bool(marker_mask.numel() > marker_mask.sum())
+        else:
+            any_masked = lambda: bool(np.asarray(marker_mask).size > np.asarray(marker_mask).sum())
+        self.use_infill = body_markers_rec is not None and any_masked()
         if body_markers_rec is not None:
-            T_['mask'], T_['rec'], T_['clbl'] = tf(marker_mask), tf(body_markers_rec), tf(contact_lbl_rec)
+            T_['mask'] = marker_mask if isinstance(marker_mask, torch.Tensor) else tf(marker_mask)
+            T_['rec'], T_['clbl'] = tf(body_markers_rec), tf(contact_lbl_rec)
             assert T_['rec'].shape[0] == B - 1 and T_['clbl'].shape == (B - 1, 4), 'body_markers_rec / contact_lbl_rec carry B - 1 frames'
         # parameters + Adam state
         self.P = {k: tf(np.asarray(params[k], np.float32).reshape(B, d)) for k, d in ENGINE_PARAMS}

@@ -209,3 +209,23 @@ def make_ae_weights(seed: int = 7, in_channel: int = 4) -> Dict[str, np.ndarray]
         w[f'dec_blc{i}.deconv2.weight'] = u((co, co, 3, 3), co * 9)
         w[f'dec_blc{i}.deconv2.bias'] = u((co,), co * 9)
     return w
+
+
+def local_faces(points: np.ndarray, F: int) -> np.ndarray:
+    """``F`` small triangles over a point cloud [V, 3]: every point with its nearest neighbours (1st + 2nd, then 3rd + 4th, ...).
+    ``make_synthetic_smplx`` draws its faces as random index triples, which is all the fitting losses need; as a SURFACE those are
+    body-sized triangles that all overlap.  What renders or queries the mesh (``lemo_amd.occlusion``) wants triangles of the size a
+    real body mesh has; put these into the model dict's ``'f'`` before creating the body model."""
+    pts = np.asarray(points, np.float64)
+    V = len(pts)
+    pairs = -(-F // V)
+    nn = np.empty((V, 2 * pairs), np.int64)
+    sq = (pts ** 2).sum(1)
+    for lo in range(0, V, 1024):
+        d = sq[lo:lo + 1024, None] - 2.0 * pts[lo:lo + 1024] @ pts.T + sq[None, :]
+        d[np.arange(len(d)), np.arange(lo, lo + len(d))] = -np.inf               # the point itself sorts first
+        nn[lo:lo + 1024] = np.argsort(d, axis=1)[:, 1:2 * pairs + 1]
+    me = np.arange(V)
+    faces = np.concatenate([np.stack([me, nn[:, 2 * k], nn[:, 2 * k + 1]], -1) for k in range(pairs)])
+    return faces[:F].astype(np.int64)
+
