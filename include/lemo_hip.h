@@ -824,6 +824,30 @@ int lemo_occlusion_query(const float* verts, int T, int V, const int* faces, int
                          float proj_fx, float proj_fy, const float* depth_scene, float thresh, unsigned* ws, float* mask,
                          float* depth_body, int* pix, void* stream);
 
+/* ---- Chamfer nearest neighbours (csrc/chamfer_kernels.hip): the `chamfer` extension of temp_prox/dist_chamfer.py:27,43 and the
+ * scene-contact term of fitting_temp_slide.py:743-753 ----
+ * xyz1 [B][N][3], xyz2 [B][M][3] (or [1][M][3] with LEMO_CHAMFER_SHARED: one target set for every batch entry, never copied); fp32,
+ * contiguous, finite.  dist1 [B][N] = the SQUARED distance (dx dx + dy dy) + dz dz of the differences to a nearest point of xyz2,
+ * idx1 [B][N] its index; ties go to the lowest index.  With LEMO_CHAMFER_REVERSE also dist2 / idx2 [B][M] (xyz2 against xyz1);
+ * otherwise they are not touched and may be NULL.  SHARED | REVERSE is refused (LEMO_ERR_ARG): that direction is not defined.
+ * split: 0 = automatic, k > 0 = cut the target range into (at most) k pieces; results do not depend on it, bit for bit.
+ * ws: lemo_chamfer_workspace_bytes(same B, N, M, flags, split) bytes of device scratch (0 bytes: may be NULL).
+ * LEMO_ERR_SHAPE: B, N or M < 1, B > 65535, B N or B M > 2^30; LEMO_ERR_ARG: null pointers, unknown flags, split < 0, a
+ * workspace that is too small.  Nothing is allocated and nothing synchronises. */
+#define LEMO_CHAMFER_SHARED 1
+#define LEMO_CHAMFER_REVERSE 2
+long long lemo_chamfer_workspace_bytes(int B, int N, int M, int flags, int split);      /* -1 for arguments the forward refuses */
+int lemo_chamfer_forward(const float* xyz1, const float* xyz2, int B, int N, int M, int flags, int split, float* dist1, int* idx1,
+                         float* dist2, int* idx2, void* ws, long long ws_bytes, void* stream);
+/* grad1[b][i] = 2 g1[b][i] (x1[b][i] - x2[b][idx1[b][i]]) + sum over {j : idx2[b][j] == i} of 2 g2[b][j] (x1[b][i] - x2[b][j]) and the mirror
+ * image for grad2 ([1][M][3], summed over the batch too, with LEMO_CHAMFER_SHARED).  g2 / idx2 are read only with LEMO_CHAMFER_REVERSE.
+ * grad1 / grad2 need no initialisation; a NULL one is neither computed nor written.  The scattered sums are fp32 atomic adds. */
+int lemo_chamfer_backward(const float* xyz1, const float* xyz2, int B, int N, int M, int flags, const float* g1, const int* idx1,
+                          const float* g2, const int* idx2, float* grad1, float* grad2, void* stream);
+/* out4 (host): queries per workgroup, targets per LDS chunk, the fewest targets an automatic split holds, and the number of
+ * workgroups at which the automatic split stops cutting the target range */
+void lemo_chamfer_sizes(int* out4);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

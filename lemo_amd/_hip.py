@@ -342,6 +342,10 @@ _SIGS = {
     'lemo_depth_raster': (C.c_int, [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(OcclCam), vp, vp]),
     'lemo_occlusion_query': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(OcclCam), C.c_float, C.c_float, vp, C.c_float,
                                        vp, vp, vp, vp, vp]),
+    'lemo_chamfer_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'lemo_chamfer_forward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong, vp]),
+    'lemo_chamfer_backward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    'lemo_chamfer_sizes': (None, [C.POINTER(C.c_int)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

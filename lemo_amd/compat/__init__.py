@@ -1,7 +1,7 @@
 """Import-compatible stand-ins for the third-party modules LEMO's hot path imports.
 
     import lemo_amd.compat.smplx as smplx         # smplx.create / smplx.lbs.lbs / smplx.lbs.transform_mat
-    import lemo_amd.compat.chamfer as chamfer     # importable, never called under the S2 / S3 configurations
+    import lemo_amd.compat.chamfer as chamfer     # chamfer.forward / backward on device tensors (csrc/chamfer_kernels.hip)
 
 ``install()`` registers them under the reference's own import names so that ``import smplx`` /
 ``from smplx.lbs import lbs`` / ``import chamfer`` inside LEMO resolve here.

@@ -86,7 +86,8 @@ class ProxTemporalFitter:
     def __init__(self, body_model: SMPLX, vposer: VPoser, smooth_encoder: Enc, ids: Dict[str, np.ndarray],
                  Xmean, Xstd, weights: dict, R, t, sdf: torch.Tensor, grid_min, grid_max, params: Dict[str, np.ndarray],
                  gt_joints, joints_conf, joint_map=None, fric_ids=None, cam: Optional[dict] = None, marker_mask=None,
-                 body_markers_rec=None, contact_lbl_rec=None, first_batch_flag: bool = False, lr: float = 0.005):
+                 body_markers_rec=None, contact_lbl_rec=None, first_batch_flag: bool = False, lr: float = 0.005,
+                 scene_v: Optional[torch.Tensor] = None, contact_verts_ids=None):
         dev = sdf.device
         self.device = dev
         f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
@@ -115,6 +116,16 @@ class ProxTemporalFitter:
         self.body_markers_rec = None if body_markers_rec is None else f(body_markers_rec)
         self.contact_lbl_rec = None if contact_lbl_rec is None else f(contact_lbl_rec)
         self.first_batch_flag = first_batch_flag
+        # body-scene contact (fitting_temp_slide.py:743-753, `contact: True`): scene vertices [M, 3] / [1, M, 3] on the device and the
+        # caller's contact vertex ids; active only with both and a positive weights['contact_loss_weight'] (default 0)
+        self.scene_v = self.contact_ids = None
+        if scene_v is not None and contact_verts_ids is not None:
+            from .chamfer import contact_ids_tensor
+            if not isinstance(scene_v, torch.Tensor) or scene_v.device != dev or scene_v.dtype != torch.float32 or scene_v.shape[-1] != 3 \
+                    or scene_v.dim() not in (2, 3) or (scene_v.dim() == 3 and scene_v.shape[0] != 1) or scene_v.numel() < 3:
+                raise ValueError('scene_v must be a float32 [M, 3] or [1, M, 3] tensor on the device of the SDF')
+            self.scene_v = scene_v.detach().reshape(1, -1, 3).contiguous()
+            self.contact_ids = contact_ids_tensor(contact_verts_ids, int(self.body_model.data.V), dev)
         self.params = [p for n, p in self.body_model.named_parameters() if p.requires_grad] + [self.pose_embedding]
         # optim_factory.py:43-46.  capturable: the step count lives on the device so that a captured step can be replayed
         self.optimizer = torch.optim.Adam(self.params, lr=lr, capturable=self.pose_embedding.is_cuda)
@@ -203,8 +214,14 @@ class ProxTemporalFitter:
         smooth = self.enc.smooth_loss(img_v) * w['motion_prior_smooth_weight']
         total = (joint_loss + pprior + shape_loss + angle + jaw + expr + lhand + rhand + sdf_pen + smooth + fric_t + fric_n +
                  infill + infill_contact)
+        # ---- body-scene contact (:743-753); without a scene, ids or a positive weight nothing is launched and total is untouched
+        contact_loss = zero
+        if self.scene_v is not None and w.get('contact_loss_weight', 0) > 0:
+            from .chamfer import contact_term
+            contact_loss = contact_term(vw, self.contact_ids, self.scene_v, w['contact_loss_weight'], _lib=self.body_model._lib_override)
+            total = total + contact_loss
         return dict(total_loss=total, joint_loss=joint_loss, s2m_dist=zero, m2s_dist=zero, self_penetration_loss=zero,
-                    sdf_penetration_loss=sdf_pen, contact_loss=zero, smooth_acc_loss=zero, smooth_vel_loss=zero,
+                    sdf_penetration_loss=sdf_pen, contact_loss=contact_loss, smooth_acc_loss=zero, smooth_vel_loss=zero,
                     motion_prior_smooth_loss=smooth, loss_fric_tangent=fric_t, loss_fric_normal=fric_n,
                     motion_infill_loss=infill, motion_infill_contact_loss=infill_contact)
 
