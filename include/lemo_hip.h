@@ -847,6 +847,35 @@ int lemo_chamfer_backward(const float* xyz1, const float* xyz2, int B, int N, in
 /* out4 (host): queries per workgroup, targets per LDS chunk, the fewest targets an automatic split holds, and the number of
  * workgroups at which the automatic split stops cutting the target range */
 void lemo_chamfer_sizes(int* out4);
+/* The one-sided search where every batch entry has its own valid points (the s2m / m2s terms, fitting_temp_slide.py:657-667).
+ * Query i of entry b is valid iff (n1 == NULL or i < n1[b]) and (q_mask == NULL or q_mask[b][i] != 0); target j likewise with n2 /
+ * t_mask.  n1, n2: int32 [B]; q_mask [B][N], t_mask [B][M]: bytes; all on the device, any of them NULL.  dist1 / idx1 [B][N]: the
+ * nearest VALID target (index into the original array, lowest index on ties); dist 0 and idx -1 for an invalid query and for every
+ * query of an entry without a valid target -- lemo_chamfer_backward(flags = 0) gives such a query no gradient.  split and ws as for
+ * lemo_chamfer_forward with lemo_chamfer_workspace_bytes(B, N, M, 0, split); results do not depend on split, bit for bit, and equal
+ * lemo_chamfer_forward's when everything is valid.  Same error codes. */
+int lemo_chamfer_masked_forward(const float* xyz1, const float* xyz2, int B, int N, int M, const int* n1, const unsigned char* q_mask,
+                                const int* n2, const unsigned char* t_mask, int split, float* dist1, int* idx1, void* ws, long long ws_bytes,
+                                void* stream);
+
+/* ---- body-vertex visibility (csrc/visibility_kernels.hip): psbody.mesh.visibility.visibility_compute(v, f, cams) with min_dist, no
+ * normals or sensors, for B frames at once (fitting_temp_slide.py:642-652) ----
+ * verts [B][V][3], faces [F][3] (shared by the frames), cam [B][3] or NULL (the origin); fp32 / int32 on the device.
+ * vis [B][V] bytes out, 1 = visible: the segment from p + min_dist (c - p) / |c - p| to the camera c meets no triangle of the frame
+ * (either side, triangles at the vertex included; degenerate triangles never hit; |c - p| <= min_dist is visible).
+ * mode: LEMO_VIS_BRUTE tests every pair; LEMO_VIS_BINNED bins the projected vertices of every frame that lies in front of the camera
+ * into a grid x grid raster (grid 0 = 64, else 2 .. 64) and lets a frame that does not take the brute-force path; LEMO_VIS_AUTO picks
+ * the faster of the two at the PROX shape.  The result does not depend on mode or grid, bit for bit.
+ * nbig [B] (or NULL): the number of triangles of each frame that took the one-workgroup-per-triangle pass (0 for brute force).
+ * ws: lemo_vertex_visibility_workspace_bytes(same B, V, F, mode, grid) bytes of device scratch (0 bytes: may be NULL).
+ * LEMO_ERR_SHAPE: B, V or F < 1, B > 65535, F > 2^30, B V > 2^30; LEMO_ERR_ARG: null pointers, an unknown mode or grid, a min_dist
+ * that is negative or not finite, a workspace that is too small.  Faces that name a vertex outside [0, V) never hit. */
+#define LEMO_VIS_AUTO 0
+#define LEMO_VIS_BRUTE 1
+#define LEMO_VIS_BINNED 2
+long long lemo_vertex_visibility_workspace_bytes(int B, int V, int F, int mode, int grid);      /* -1 for arguments the launch refuses */
+int lemo_vertex_visibility(const float* verts, int B, int V, const int* faces, int F, const float* cam, float min_dist, int mode, int grid,
+                           unsigned char* vis, int* nbig, void* ws, long long ws_bytes, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

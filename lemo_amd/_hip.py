@@ -346,6 +346,9 @@ _SIGS = {
     'lemo_chamfer_forward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong, vp]),
     'lemo_chamfer_backward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     'lemo_chamfer_sizes': (None, [C.POINTER(C.c_int)]),
+    'lemo_chamfer_masked_forward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_longlong, vp]),
+    'lemo_vertex_visibility_workspace_bytes': (C.c_longlong, [C.c_int] * 5),
+    'lemo_vertex_visibility': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, C.c_longlong, vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

@@ -2,18 +2,22 @@
 
     import lemo_amd.compat.smplx as smplx         # smplx.create / smplx.lbs.lbs / smplx.lbs.transform_mat
     import lemo_amd.compat.chamfer as chamfer     # chamfer.forward / backward on device tensors (csrc/chamfer_kernels.hip)
+    import lemo_amd.compat.psbody.mesh            # Mesh, visibility.visibility_compute (csrc/visibility_kernels.hip)
 
 ``install()`` registers them under the reference's own import names so that ``import smplx`` /
-``from smplx.lbs import lbs`` / ``import chamfer`` inside LEMO resolve here.
+``from smplx.lbs import lbs`` / ``import chamfer`` / ``from psbody.mesh.visibility import visibility_compute`` inside LEMO resolve here.
 """
 import sys
 
 
 def install(force: bool = False) -> None:
-    """``sys.modules['smplx']``, ``['smplx.lbs']`` and ``['chamfer']`` -> this package (existing entries are kept
-    unless ``force``)."""
-    from . import chamfer, smplx
+    """``sys.modules['smplx']``, ``['smplx.lbs']``, ``['chamfer']``, ``['psbody']``, ``['psbody.mesh']`` and
+    ``['psbody.mesh.visibility']`` -> this package (existing entries are kept unless ``force``)."""
+    from . import chamfer, psbody, smplx
+    from .psbody import mesh
+    from .psbody.mesh import visibility
     from .smplx import lbs
-    for name, mod in (('smplx', smplx), ('smplx.lbs', lbs), ('chamfer', chamfer)):
+    for name, mod in (('smplx', smplx), ('smplx.lbs', lbs), ('chamfer', chamfer), ('psbody', psbody), ('psbody.mesh', mesh),
+                      ('psbody.mesh.visibility', visibility)):
         if force or name not in sys.modules:
             sys.modules[name] = mod

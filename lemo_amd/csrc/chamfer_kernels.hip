@@ -19,6 +19,14 @@
 // the caller's workspace and chamfer_combine_kernel folds them.  fp32 VALU only: per pair 3 subtractions, 1 multiply, 2 fused
 // multiply-adds, 1 compare and 2 selects; there is no matrix-core form of an arg-min.
 //
+// Masked form (chamfer_masked_forward: the scan-to-mesh / mesh-to-scan terms of fitting_temp_slide.py:657-667, where every frame has
+// its own number of valid scan points and its own visible vertices).  The same kernel, instantiated with MASKED: an invalid target is
+// staged into LDS as +inf coordinates, exactly like the lanes past the end of a chunk, so it never passes the strict <; valid means
+// index < n[b] (where a count is given) AND mask[b][index] != 0 (where a mask is given).  Indices refer to the original arrays.  An
+// invalid query, and every query of an entry without a valid target, reports dist = 0 and idx = -1, which the backward kernels already
+// read as "no gradient".  Nothing is compacted and nothing waits for the device.  Everything above carries over: the same three
+// operations per pair, lowest index on ties among the valid targets, the same bits for every split count.
+//
 // Backward, as the extension defines it: grad1[i] = 2 g1[i] (x1[i] - x2[idx1[i]]) + sum_{j: idx2[j] = i} 2 g2[j] (x1[i] - x2[j]) and the
 // mirror image.  The own-side term is a plain store (or a memset where that direction was not computed); the scattered term is an fp32
 // atomicAdd, launched after the stores.  A side whose gradient pointer is NULL is neither computed nor written.
@@ -36,15 +44,31 @@ namespace lemo {
 #define CH_TARGET_WGS 1024                                   // workgroups wanted before the target range stops being split (4 per CU)
 #define CH_MAX_SPLITS 1024
 
+struct ChMask {                                              // MASKED only; any of the four may be NULL
+  const int* n1; const unsigned char* qm;                    // valid leading queries [B], query mask [B][N]
+  const int* n2; const unsigned char* tm;                    // valid leading targets [B], target mask [B][M]
+  int fin;                                                   // this launch writes the final result (no combine follows)
+};
+
+__device__ __forceinline__ bool ch_query_valid(const ChMask& mk, int b, int N, int i) {
+  return (!mk.n1 || i < mk.n1[b]) && (!mk.qm || mk.qm[(size_t)b * N + i] != 0);
+}
+
 // queries q of [0, N) against targets [t0, t1) of one batch entry; grid (query block, split, batch)
+template <bool MASKED>
 __global__ void __launch_bounds__(CH_BLOCK) chamfer_nn_kernel(const float* __restrict__ xq, const float* __restrict__ xt, int N, int M,
                                                               long long tstride, int split_len, float* __restrict__ dist,
-                                                              int* __restrict__ idx, long long ostride) {
+                                                              int* __restrict__ idx, long long ostride, ChMask mk) {
   __shared__ __attribute__((aligned(16))) float sx[2][CH_CHUNK];
   __shared__ __attribute__((aligned(16))) float sy[2][CH_CHUNK];
   __shared__ __attribute__((aligned(16))) float sz[2][CH_CHUNK];
   const int tid = threadIdx.x, b = blockIdx.z, sp = blockIdx.y;
-  const int t0 = sp * split_len, t1 = min(M, t0 + split_len);
+  const int t0 = sp * split_len;
+  int t1 = min(M, t0 + split_len);
+  if constexpr (MASKED) {                                    // targets past the count are invalid: the range ends there; a workgroup
+    if (mk.n2) t1 = min(t1, mk.n2[b]);                       // whose queries all lie past the count scans nothing (uniform)
+    if (mk.n1 && (int)(blockIdx.x * CH_QPW) >= mk.n1[b]) t1 = t0;
+  }
   const float* __restrict__ q = xq + (size_t)b * N * 3;
   const float* __restrict__ t = xt + (size_t)b * tstride;
   const int q0 = blockIdx.x * CH_QPW + tid;
@@ -67,7 +91,9 @@ __global__ void __launch_bounds__(CH_BLOCK) chamfer_nn_kernel(const float* __res
 #pragma unroll
     for (int r = 0; r < PER; ++r) {
       const int e = tid + r * CH_BLOCK;
-      stage[r] = e < lim ? t[base + e] : INFINITY;
+      bool ok = e < lim;
+      if constexpr (MASKED) ok = ok && (!mk.tm || mk.tm[(size_t)b * M + c0 + e / 3] != 0);
+      stage[r] = ok ? t[base + e] : INFINITY;
     }
   };
   auto put = [&](int buf) {
@@ -114,21 +140,33 @@ __global__ void __launch_bounds__(CH_BLOCK) chamfer_nn_kernel(const float* __res
 #pragma unroll
   for (int k = 0; k < CH_QPT; ++k) {
     const int i = q0 + k * CH_BLOCK;
-    if (i < N) { od[i] = best[k]; oi[i] = bi[k]; }
+    if (i >= N) continue;
+    if constexpr (MASKED) {
+      if (mk.fin && (!(best[k] < INFINITY) || !ch_query_valid(mk, b, N, i))) { od[i] = 0.f; oi[i] = -1; continue; }
+    }
+    od[i] = best[k]; oi[i] = bi[k];
   }
 }
 
 // fold S partial results [S][n] in ascending split order: a later split wins only with a strictly smaller distance
+template <bool MASKED>
 __global__ void __launch_bounds__(CH_BLOCK) chamfer_combine_kernel(const float* __restrict__ pd, const int* __restrict__ pi, int S,
-                                                                   long long n, float* __restrict__ dist, int* __restrict__ idx) {
+                                                                   long long n, float* __restrict__ dist, int* __restrict__ idx, int N,
+                                                                   ChMask mk) {
   const long long i = (long long)blockIdx.x * CH_BLOCK + threadIdx.x;
   if (i >= n) return;
+  if constexpr (MASKED) {                                    // the partial results of an invalid query are never read
+    if (!ch_query_valid(mk, (int)(i / N), N, (int)(i % N))) { dist[i] = 0.f; idx[i] = -1; return; }
+  }
   float best = pd[i];
   int bi = pi[i];
   for (int s = 1; s < S; ++s) {
     const float d = pd[(size_t)s * n + i];
     const int j = pi[(size_t)s * n + i];
     if (d < best) { best = d; bi = j; }
+  }
+  if constexpr (MASKED) {
+    if (!(best < INFINITY)) { best = 0.f; bi = -1; }          // no valid target in any range
   }
   dist[i] = best;
   idx[i] = bi;
@@ -196,21 +234,25 @@ long long ch_ws_elems(int Bq, int Nq, int Mt, int split) {
   return S > 1 ? (long long)S * Bq * Nq : 0;
 }
 
+template <bool MASKED>
 int ch_nn(const float* xq, const float* xt, int Bq, int Nq, int Mt, long long tstride, int split, float* dist, int* idx, void* ws,
-          long long ws_bytes, hipStream_t s) {
+          long long ws_bytes, hipStream_t s, ChMask mk = ChMask{nullptr, nullptr, nullptr, nullptr, 0}) {
   const int len = ch_split_len(Bq, Nq, Mt, split);
   const int S = (Mt + len - 1) / len;
   const long long n = (long long)Bq * Nq;
   const dim3 grid((Nq + CH_QPW - 1) / CH_QPW, S, Bq);
   if (S == 1) {
-    hipLaunchKernelGGL(chamfer_nn_kernel, grid, dim3(CH_BLOCK), 0, s, xq, xt, Nq, Mt, tstride, len, dist, idx, 0ll);
+    mk.fin = 1;
+    hipLaunchKernelGGL((chamfer_nn_kernel<MASKED>), grid, dim3(CH_BLOCK), 0, s, xq, xt, Nq, Mt, tstride, len, dist, idx, 0ll, mk);
     return (int)hipGetLastError();
   }
   if (!ws || ws_bytes < (long long)S * n * 8) return LEMO_ERR_ARG;
   float* pd = static_cast<float*>(ws);
   int* pi = reinterpret_cast<int*>(pd + (size_t)S * n);
-  hipLaunchKernelGGL(chamfer_nn_kernel, grid, dim3(CH_BLOCK), 0, s, xq, xt, Nq, Mt, tstride, len, pd, pi, n);
-  hipLaunchKernelGGL(chamfer_combine_kernel, dim3((unsigned)((n + CH_BLOCK - 1) / CH_BLOCK)), dim3(CH_BLOCK), 0, s, pd, pi, S, n, dist, idx);
+  mk.fin = 0;
+  hipLaunchKernelGGL((chamfer_nn_kernel<MASKED>), grid, dim3(CH_BLOCK), 0, s, xq, xt, Nq, Mt, tstride, len, pd, pi, n, mk);
+  hipLaunchKernelGGL((chamfer_combine_kernel<MASKED>), dim3((unsigned)((n + CH_BLOCK - 1) / CH_BLOCK)), dim3(CH_BLOCK), 0, s, pd, pi, S, n, dist,
+                     idx, Nq, mk);
   return (int)hipGetLastError();
 }
 
@@ -230,10 +272,19 @@ int chamfer_forward(const float* xyz1, const float* xyz2, int B, int N, int M, i
   if (int e = ch_shape(B, N, M, flags, c)) return e;
   if (!xyz1 || !xyz2 || !dist1 || !idx1 || split < 0 || ws_bytes < 0) return LEMO_ERR_ARG;
   if (c.reverse && (!dist2 || !idx2)) return LEMO_ERR_ARG;
-  int e = c.shared ? ch_nn(xyz1, xyz2, 1, B * N, M, 0, split, dist1, idx1, ws, ws_bytes, s)
-                   : ch_nn(xyz1, xyz2, B, N, M, 3ll * M, split, dist1, idx1, ws, ws_bytes, s);
+  int e = c.shared ? ch_nn<false>(xyz1, xyz2, 1, B * N, M, 0, split, dist1, idx1, ws, ws_bytes, s)
+                   : ch_nn<false>(xyz1, xyz2, B, N, M, 3ll * M, split, dist1, idx1, ws, ws_bytes, s);
   if (e || !c.reverse) return e;
-  return ch_nn(xyz2, xyz1, B, M, N, 3ll * N, split, dist2, idx2, ws, ws_bytes, s);        // the workspace is reused in stream order
+  return ch_nn<false>(xyz2, xyz1, B, M, N, 3ll * N, split, dist2, idx2, ws, ws_bytes, s);        // the workspace is reused in stream order
+}
+
+int chamfer_masked_forward(const float* xyz1, const float* xyz2, int B, int N, int M, const int* n1, const unsigned char* q_mask,
+                           const int* n2, const unsigned char* t_mask, int split, float* dist1, int* idx1, void* ws, long long ws_bytes,
+                           hipStream_t s) {
+  ChShape c;
+  if (int e = ch_shape(B, N, M, 0, c)) return e;
+  if (!xyz1 || !xyz2 || !dist1 || !idx1 || split < 0 || ws_bytes < 0) return LEMO_ERR_ARG;
+  return ch_nn<true>(xyz1, xyz2, B, N, M, 3ll * M, split, dist1, idx1, ws, ws_bytes, s, ChMask{n1, q_mask, n2, t_mask, 0});
 }
 
 int chamfer_backward(const float* xyz1, const float* xyz2, int B, int N, int M, int flags, const float* g1, const int* idx1,
@@ -279,4 +330,9 @@ int lemo_chamfer_backward(const float* xyz1, const float* xyz2, int B, int N, in
   return lemo::chamfer_backward(xyz1, xyz2, B, N, M, flags, g1, idx1, g2, idx2, grad1, grad2, (hipStream_t)stream);
 }
 void lemo_chamfer_sizes(int* out4) { lemo::chamfer_sizes(out4); }
+int lemo_chamfer_masked_forward(const float* xyz1, const float* xyz2, int B, int N, int M, const int* n1, const unsigned char* q_mask,
+                                const int* n2, const unsigned char* t_mask, int split, float* dist1, int* idx1, void* ws, long long ws_bytes,
+                                void* stream) {
+  return lemo::chamfer_masked_forward(xyz1, xyz2, B, N, M, n1, q_mask, n2, t_mask, split, dist1, idx1, ws, ws_bytes, (hipStream_t)stream);
+}
 }  // extern "C"

@@ -87,7 +87,8 @@ class ProxTemporalFitter:
                  Xmean, Xstd, weights: dict, R, t, sdf: torch.Tensor, grid_min, grid_max, params: Dict[str, np.ndarray],
                  gt_joints, joints_conf, joint_map=None, fric_ids=None, cam: Optional[dict] = None, marker_mask=None,
                  body_markers_rec=None, contact_lbl_rec=None, first_batch_flag: bool = False, lr: float = 0.005,
-                 scene_v: Optional[torch.Tensor] = None, contact_verts_ids=None):
+                 scene_v: Optional[torch.Tensor] = None, contact_verts_ids=None, scan: Optional[torch.Tensor] = None,
+                 scan_point_num: Optional[torch.Tensor] = None, body_mask: Optional[torch.Tensor] = None):
         dev = sdf.device
         self.device = dev
         f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
@@ -126,6 +127,25 @@ class ProxTemporalFitter:
                 raise ValueError('scene_v must be a float32 [M, 3] or [1, M, 3] tensor on the device of the SDF')
             self.scene_v = scene_v.detach().reshape(1, -1, 3).contiguous()
             self.contact_ids = contact_ids_tensor(contact_verts_ids, int(self.body_model.data.V), dev)
+        # scan-to-mesh / mesh-to-scan (fitting_temp_slide.py:637-670, `s2m: True` / `m2s: True`): the padded scan [B, S, 3] in camera
+        # coordinates, its valid counts [B] and the body mask [V], all on the device; active only with all three and a positive
+        # weights['s2m_weight'] / weights['m2s_weight'] (default 0).  The counts are checked here, once.
+        self.scan = self.scan_point_num = self.body_mask = None
+        if scan is not None and scan_point_num is not None and body_mask is not None:
+            V = int(self.body_model.data.V)
+            if not isinstance(scan, torch.Tensor) or scan.device != dev or scan.dtype != torch.float32 or scan.dim() != 3 or \
+                    scan.shape[0] != B or scan.shape[1] < 1 or scan.shape[2] != 3:
+                raise ValueError(f'scan must be a float32 [B = {B}, S, 3] tensor on the device of the SDF')
+            if not isinstance(scan_point_num, torch.Tensor) or scan_point_num.device != dev or scan_point_num.dtype != torch.int32 or \
+                    tuple(scan_point_num.shape) != (B,):
+                raise ValueError(f'scan_point_num must be an int32 [{B}] tensor on the device of the SDF')
+            if int(scan_point_num.min()) < 0 or int(scan_point_num.max()) > scan.shape[1]:
+                raise ValueError(f'scan_point_num must lie in 0 .. S = {scan.shape[1]}')
+            if not isinstance(body_mask, torch.Tensor) or body_mask.device != dev or body_mask.dtype != torch.bool or \
+                    tuple(body_mask.shape) != (V,):
+                raise ValueError(f'body_mask must be a bool [{V}] tensor on the device of the SDF')
+            self.scan, self.scan_point_num, self.body_mask = scan.detach().contiguous(), scan_point_num.contiguous(), body_mask.contiguous()
+            self._scan_faces = torch.from_numpy(np.ascontiguousarray(self.body_model.faces, np.int32)).to(dev)     # uploaded once
         self.params = [p for n, p in self.body_model.named_parameters() if p.requires_grad] + [self.pose_embedding]
         # optim_factory.py:43-46.  capturable: the step count lives on the device so that a captured step can be replayed
         self.optimizer = torch.optim.Adam(self.params, lr=lr, capturable=self.pose_embedding.is_cuda)
@@ -220,7 +240,15 @@ class ProxTemporalFitter:
             from .chamfer import contact_term
             contact_loss = contact_term(vw, self.contact_ids, self.scene_v, w['contact_loss_weight'], _lib=self.body_model._lib_override)
             total = total + contact_loss
-        return dict(total_loss=total, joint_loss=joint_loss, s2m_dist=zero, m2s_dist=zero, self_penetration_loss=zero,
+        # ---- scan-to-mesh / mesh-to-scan (:637-670) on the camera-space vertices; same rule: nothing is launched without a weight
+        s2m_dist, m2s_dist = zero, zero
+        if self.scan is not None and (w.get('s2m_weight', 0) > 0 or w.get('m2s_weight', 0) > 0):
+            from .scan import scan_terms
+            s2m_dist, m2s_dist = scan_terms(verts, self._scan_faces, self.scan, self.scan_point_num, self.body_mask, w.get('s2m_weight', 0),
+                                            w.get('m2s_weight', 0), w.get('rho_s2m', 1), w.get('rho_m2s', 1), check_counts=False,
+                                            _lib=bm._lib_override)
+            total = total + (s2m_dist + m2s_dist)
+        return dict(total_loss=total, joint_loss=joint_loss, s2m_dist=s2m_dist, m2s_dist=m2s_dist, self_penetration_loss=zero,
                     sdf_penetration_loss=sdf_pen, contact_loss=contact_loss, smooth_acc_loss=zero, smooth_vel_loss=zero,
                     motion_prior_smooth_loss=smooth, loss_fric_tangent=fric_t, loss_fric_normal=fric_n,
                     motion_infill_loss=infill, motion_infill_contact_loss=infill_contact)
