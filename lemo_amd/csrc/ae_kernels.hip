@@ -150,7 +150,7 @@ int stuff2_fwd(const float* in, int h, int w, float* out, int H, int W, int C, h
   return (int)hipGetLastError();
 }
 int stuff2_bwd(const float* dout, int H, int W, const float* act, float* din, int h, int w, int C, hipStream_t s) {
-  if (C % 8) return LEMO_ERR_SHAPE;
+  if (C % 8 || 2 * (h - 1) > H - 1 || 2 * (w - 1) > W - 1) return LEMO_ERR_SHAPE;      // the gather reads dout[2i][2j]
   const int n = (C / 8) * h * w;
   hipLaunchKernelGGL(stuff2_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, s, dout, H, W, act, din, h, w, C);
   return (int)hipGetLastError();
@@ -197,7 +197,7 @@ conv3x3_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x, 
     const int p = (PB) + 2 * u + kk;                                                               \
     const bool ok = p < p1;                                                                        \
     const int pc = ok ? p : p1 - 1;                                                                \
-    const int y = (int)__umulhi((unsigned)pc, wmagic), xx = pc - y * W;   /* p / W, host-made magic */ \
+    const int y = wmagic ? (int)__umulhi((unsigned)pc, wmagic) : pc, xx = pc - y * W;   /* p / W (wgrad_magic) */ \
     const int q = (y + 1) * Wp + (xx + 1);                                                         \
     const float av = ap[(size_t)q * 8];                                                            \
     const float bv = bp[(size_t)(q + dyo * Wp + dxo) * 8];                                         \
@@ -271,6 +271,10 @@ conv3x3_wgrad_reduce_kernel(const float* __restrict__ partial, int nslab, int ci
 
 int conv3x3_wgrad_nslab(int H, int W) { return (H * W + WG_SLAB - 1) / WG_SLAB; }
 
+// p / W as __umulhi(p, magic) with magic = 2^32 / W + 1: exact for p < 2^32 / W.  W = 1 has no such magic (2^32 + 1 does not
+// fit and would truncate to 1, i.e. y = 0 for every pixel): 0 tells the kernel that a pixel is its own row.
+static unsigned wgrad_magic(int W) { return W == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)W + 1); }
+
 // All weight-gradient reductions of a training step in ONE launch (the AE has 20 layers: 20 reduce launches of ~12 us, most of
 // it launch latency, become one).  Same per-element arithmetic as conv3x3_wgrad_reduce_kernel (slab order), so the
 // gradients have the same bits.  jobs: by value in the kernel argument (<= LEMO_WGRAD_MAX_JOBS).
@@ -319,7 +323,7 @@ conv3x3_wgrad_reduce_multi_kernel(WgradJobs J) {
 int conv3x3_wgrad_partial(const float* dy, const float* x, int H, int W, int cin, int cout, float* partial, hipStream_t s) {
   if (cin % 8 || cout % 32 || H < 1 || W < 1 || (long)H * W > (1l << 24)) return LEMO_ERR_SHAPE;
   const int nslab = conv3x3_wgrad_nslab(H, W);
-  const unsigned wmagic = (unsigned)((1ull << 32) / (unsigned)W + 1);
+  const unsigned wmagic = wgrad_magic(W);
   const int ntile = nslab * 9 * (cout / 32) * ((cin + 31) / 32);
   hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3(ntile), dim3(256), 0, s, dy, x, H, W, wmagic, cin, cout, partial, nslab);
   return (int)hipGetLastError();
@@ -348,7 +352,7 @@ int conv3x3_wgrad(const float* dy, const float* x, int H, int W, int cin, int co
                   float* partial, float* dw, float* db, hipStream_t s) {
   if (cin % 8 || cout % 32 || cin_real > cin || cout_real > cout || H < 1 || W < 1 || (long)H * W > (1l << 24)) return LEMO_ERR_SHAPE;
   const int nslab = conv3x3_wgrad_nslab(H, W);
-  const unsigned wmagic = (unsigned)((1ull << 32) / (unsigned)W + 1);          // exact for p < 2^32 / W
+  const unsigned wmagic = wgrad_magic(W);
   const int ntile = nslab * 9 * (cout / 32) * ((cin + 31) / 32);
   hipLaunchKernelGGL(conv3x3_wgrad_kernel, dim3(ntile), dim3(256), 0, s, dy, x, H, W, wmagic, cin, cout, partial, nslab);
   int e = (int)hipGetLastError();

@@ -456,7 +456,9 @@ int conv_split_init() {
 
 // shapes the split kernel takes; everything else stays on conv3x3_mfma_lds
 bool conv3x3_split_supported(int H, int W, int cin, int cout) {
-  if ((cin != 32 && cin != 64) || (cout != 32 && cout != 64) || H <= 0 || W <= 0) return false;
+  // W = 1 is refused: div_w's magic 2^32 / W + 1 does not fit 32 bits there (it would truncate to 1 and every pixel would land
+  // in row 0).  Every launch of conv3x3_split_kernel is behind this predicate, so W = 1 cannot reach div_w.
+  if ((cin != 32 && cin != 64) || (cout != 32 && cout != 64) || H <= 0 || W < 2) return false;
   const long P = (long)H * W;
   const long full = P / 128;
   if (full < 1 || P > (1l << 24)) return false;

@@ -19,10 +19,13 @@ __device__ __forceinline__ float sdf_at(const SdfVol& v, float px, float py, flo
   const float nx = (px - v.g0[0]) * v.sc[0] - 1.f, ny = (py - v.g0[1]) * v.sc[1] - 1.f, nz = (pz - v.g0[2]) * v.sc[2] - 1.f;
   // unnormalise (align_corners = False) and clamp to the border
   float fw = ((nz + 1.f) * W - 1.f) * 0.5f, fh = ((ny + 1.f) * H - 1.f) * 0.5f, fd = ((nx + 1.f) * D - 1.f) * 0.5f;
-  float mw = 1.f, mh = 1.f, md = 1.f;                    // gradient multipliers (0 where clamped)
-  if (fw < 0.f) { fw = 0.f; mw = 0.f; } else if (fw > (float)(W - 1)) { fw = (float)(W - 1); mw = 0.f; }
-  if (fh < 0.f) { fh = 0.f; mh = 0.f; } else if (fh > (float)(H - 1)) { fh = (float)(H - 1); mh = 0.f; }
-  if (fd < 0.f) { fd = 0.f; md = 0.f; } else if (fd > (float)(D - 1)) { fd = (float)(D - 1); md = 0.f; }
+  // gradient multipliers (0 where clamped).  torch's clip_coordinates_set_grad takes the border itself as clamped (in <= 0, in >=
+  // size - 1): a point exactly on the first voxel centre has gradient 0, not the slope of the first cell.  On the last centre the
+  // slope is 0 anyway (both corners are the last voxel), so `>` and `>=` are the same there.
+  float mw = 1.f, mh = 1.f, md = 1.f;
+  if (fw <= 0.f) { fw = 0.f; mw = 0.f; } else if (fw > (float)(W - 1)) { fw = (float)(W - 1); mw = 0.f; }
+  if (fh <= 0.f) { fh = 0.f; mh = 0.f; } else if (fh > (float)(H - 1)) { fh = (float)(H - 1); mh = 0.f; }
+  if (fd <= 0.f) { fd = 0.f; md = 0.f; } else if (fd > (float)(D - 1)) { fd = (float)(D - 1); md = 0.f; }
   const float w0f = floorf(fw), h0f = floorf(fh), d0f = floorf(fd);
   const int w0 = (int)w0f, h0 = (int)h0f, d0 = (int)d0f;
   const float tw = fw - w0f, th = fh - h0f, td = fd - d0f;
