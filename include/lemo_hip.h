@@ -877,6 +877,40 @@ long long lemo_vertex_visibility_workspace_bytes(int B, int V, int F, int mode, 
 int lemo_vertex_visibility(const float* verts, int B, int V, const int* faces, int F, const float* cam, float min_dist, int mode, int grid,
                            unsigned char* vis, int* nbig, void* ws, long long ws_bytes, void* stream);
 
+/* ---- depth frames to body scans (csrc/depth_scan_kernels.hip): Projection.create_scan (temp_prox/projection_utils.py:35-90) and the
+ * truncate / pad / mean of temp_prox/data_parser_slide.py:283-323, for B frames of H x W depth pixels at once ----
+ * The calibration: rays [H][W][2] (device, fp32): the undistorted normalised IR coordinate of every depth pixel (built once per
+ * calibration on the host); everything else is host data, row-major: view_d = [R_d | t_d] (3 x 4) of the IR camera; Rc (3 x 3, from
+ * the colour camera's Rodrigues vector), Tc, fx / fy / cx / cy, k = (k1, k2, p1, p2, k3) of the colour camera; view_c (3 x 4) its view
+ * matrix; cW x cH the colour image. */
+typedef struct lemo_depth_calib {
+  const float* rays;
+  float view_d[12];
+  float Rc[9], Tc[3];
+  float fx, fy, cx, cy;
+  float k[5];
+  float view_c[12];
+  int cW, cH;
+} lemo_depth_calib;
+/* depth [B][H][W]: float32 metres (raw = 0) or uint16 with d = raw / 8 * depth_scale (raw = 1); flip = 1 reads the frame mirrored
+ * left-right.  mask: bytes, [B][cH][cW] looked up at the rounded colour pixel (mask_on_color = 1), or [B][H][W] with the depth taken as
+ * 0 where it is non-zero (mask_on_color = 0; the caller's depth is not modified).  A pixel is valid iff its depth is finite, the z of
+ * its point exceeds TH and, with mask_on_color, its colour pixel lies inside the image and the mask is 0 there.  coord_color = 1 gives
+ * points in the colour camera's frame (view_c . (p, 1)), 0 the unprojected p.
+ * Out: scan [B][S][3]: the first S valid points of each frame in row-major pixel order, zeros behind them (no initialisation
+ * needed); n_valid [B]: the valid pixels; scan_point_num [B] = min(n_valid, S); init_trans [B][3]: the mean of ALL valid points (NaN
+ * without any); optionally (both or neither) points [B][H][W][3] and valid [B][H][W]: every pixel's point and flag -- the scan holds
+ * exactly those bits.  Deterministic.  ws: lemo_depth_scan_ws_bytes(B, H, W) bytes of device scratch, 8-byte aligned.
+ * LEMO_ERR_SHAPE: B, H, W or S < 1, B > 1024, H W > 2^22, S > 2^20, cW or cH outside [1, 32768]; LEMO_ERR_ARG: null pointers, a flag
+ * that is not 0 / 1, depth_scale or TH not finite, a workspace that is too small.  Nothing is launched then. */
+long long lemo_depth_scan_ws_bytes(int B, int H, int W);      /* -1 for shapes the launch refuses */
+int lemo_depth_scan(const void* depth, int raw, int flip, float depth_scale, const unsigned char* mask, int mask_on_color, int coord_color,
+                    float TH, const lemo_depth_calib* cal, int B, int H, int W, int S, float* scan, int* scan_point_num, int* n_valid,
+                    float* init_trans, float* points, unsigned char* valid, void* ws, long long ws_bytes, void* stream);
+/* points [B][H][W][3] = unproject_depth_image of every frame (projection_utils.py:35-48); the colour camera's fields are not read */
+int lemo_depth_unproject(const void* depth, int raw, int flip, float depth_scale, const lemo_depth_calib* cal, int B, int H, int W,
+                         float* points, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

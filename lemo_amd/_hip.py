@@ -109,6 +109,12 @@ class OcclCam(C.Structure):
                 ('W', C.c_int), ('H', C.c_int), ('cull_backface', C.c_int)]
 
 
+class DepthCalib(C.Structure):
+    """lemo_depth_calib"""
+    _fields_ = [('rays', vp), ('view_d', C.c_float * 12), ('Rc', C.c_float * 9), ('Tc', C.c_float * 3), ('fx', C.c_float), ('fy', C.c_float),
+                ('cx', C.c_float), ('cy', C.c_float), ('k', C.c_float * 5), ('view_c', C.c_float * 12), ('cW', C.c_int), ('cH', C.c_int)]
+
+
 class SkinConst(C.Structure):
     _fields_ = [('V', C.c_int), ('NC', C.c_int), ('KW', C.c_int), ('blend_fp32', C.c_int)] + \
         [(n, vp) for n in ('Dg', 'v_template', 'w_idx', 'w_val', 'DgH')] + [('dgh_inv', C.c_float)]
@@ -349,6 +355,10 @@ _SIGS = {
     'lemo_chamfer_masked_forward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_longlong, vp]),
     'lemo_vertex_visibility_workspace_bytes': (C.c_longlong, [C.c_int] * 5),
     'lemo_vertex_visibility': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, C.c_longlong, vp]),
+    'lemo_depth_scan_ws_bytes': (C.c_longlong, [C.c_int] * 3),
+    'lemo_depth_scan': (C.c_int, [vp, C.c_int, C.c_int, C.c_float, vp, C.c_int, C.c_int, C.c_float, C.POINTER(DepthCalib)] + [C.c_int] * 4 +
+                        [vp] * 7 + [C.c_longlong, vp]),
+    'lemo_depth_unproject': (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.POINTER(DepthCalib), C.c_int, C.c_int, C.c_int, vp, vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
