@@ -911,6 +911,36 @@ int lemo_depth_scan(const void* depth, int raw, int flip, float depth_scale, con
 int lemo_depth_unproject(const void* depth, int raw, int flip, float depth_scale, const lemo_depth_calib* cal, int B, int H, int W,
                          float* points, void* stream);
 
+/* ---- self-penetration (csrc/selfpen_kernels.hip): mesh_intersection's BVH search + FilterFaces + DistanceFieldPenetrationLoss
+ * (fitting_temp_slide.py:618-635) for B frames at once; the behaviour is the one written in that file's header, not a run of the
+ * package ----
+ * verts [B][V][3] fp32, faces [F][3] int32 (shared by the frames); optional segm [F], parents [F] (int32) and ign [P][P] bytes
+ * (P <= 64; parents and ign need segm).  Triangles i < j of a frame collide iff they share no vertex index, their boxes overlap, an
+ * edge of one meets the other (Moeller-Trumbore, inclusive, either side, a zero determinant never hits) and the segmentation does
+ * not exclude them; a face with a vertex outside [0, V) or a coordinate that is not finite never collides.
+ * pairs [B][C][2] out: the colliding pairs in lexicographic order, -1 behind the last, the first C on overflow; count [B] out: the
+ * true number (saturates at 2^31 - 1).  Deterministic, no host synchronisation, no allocation.  mode: LEMO_SELFPEN_BRUTE tests
+ * every pair behind a box reject, LEMO_SELFPEN_GRID bins the faces of every frame into a grid^3 lattice (grid 0 = 16, else 2 .. 16),
+ * LEMO_SELFPEN_AUTO picks the faster at the PROX shape; the result does not depend on mode or grid, bit for bit.
+ * ws: lemo_selfpen_search_workspace_bytes(same B, V, F, mode, grid) bytes of device scratch.
+ * LEMO_ERR_SHAPE: B, V, F or C < 1, B > 65535, F > 2^24, B V or B F > 2^30, B C > 2^28; LEMO_ERR_ARG: null pointers, an unknown mode
+ * or grid, P outside 0 .. 64 or inconsistent with ign, a workspace that is too small.  Nothing is launched then. */
+#define LEMO_SELFPEN_AUTO 0
+#define LEMO_SELFPEN_BRUTE 1
+#define LEMO_SELFPEN_GRID 2
+long long lemo_selfpen_search_workspace_bytes(int B, int V, int F, int mode, int grid);         /* -1 for arguments the launch refuses */
+int lemo_selfpen_search(const float* verts, int B, int V, const int* faces, int F, const int* segm, const int* parents, const unsigned char* ign,
+                        int P, int mode, int grid, int* pairs, int C, int* count, void* ws, long long ws_bytes, void* stream);
+/* loss [B] out: the cone distance field of the receiving triangle at the intruding triangle's corners, squared, both ways, summed
+ * over the first min(count[b], C) pairs of each frame (count NULL: all C; an entry that names no face is skipped).  sigma > 0.
+ * Deterministic.  A zero-area triangle contributes nothing. */
+int lemo_selfpen_loss_forward(const float* verts, int B, int V, const int* faces, int F, const int* pairs, int C, const int* count, float sigma,
+                              int penalize_outside, float* loss, void* stream);
+/* gverts [B][V][3] out (zeroed here) = sum_b gloss[b] dL[b] / dverts: through the points and through the normal, circumcentre and
+ * circumradius of the receiving triangles; fp32 atomic adds. */
+int lemo_selfpen_loss_backward(const float* verts, int B, int V, const int* faces, int F, const int* pairs, int C, const int* count, float sigma,
+                               int penalize_outside, const float* gloss, float* gverts, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

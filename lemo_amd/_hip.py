@@ -359,6 +359,10 @@ _SIGS = {
     'lemo_depth_scan': (C.c_int, [vp, C.c_int, C.c_int, C.c_float, vp, C.c_int, C.c_int, C.c_float, C.POINTER(DepthCalib)] + [C.c_int] * 4 +
                         [vp] * 7 + [C.c_longlong, vp]),
     'lemo_depth_unproject': (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.POINTER(DepthCalib), C.c_int, C.c_int, C.c_int, vp, vp]),
+    'lemo_selfpen_search_workspace_bytes': (C.c_longlong, [C.c_int] * 5),
+    'lemo_selfpen_search': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_longlong, vp]),
+    'lemo_selfpen_loss_forward': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, vp]),
+    'lemo_selfpen_loss_backward': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, vp, vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

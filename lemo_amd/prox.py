@@ -88,7 +88,8 @@ class ProxTemporalFitter:
                  gt_joints, joints_conf, joint_map=None, fric_ids=None, cam: Optional[dict] = None, marker_mask=None,
                  body_markers_rec=None, contact_lbl_rec=None, first_batch_flag: bool = False, lr: float = 0.005,
                  scene_v: Optional[torch.Tensor] = None, contact_verts_ids=None, scan: Optional[torch.Tensor] = None,
-                 scan_point_num: Optional[torch.Tensor] = None, body_mask: Optional[torch.Tensor] = None):
+                 scan_point_num: Optional[torch.Tensor] = None, body_mask: Optional[torch.Tensor] = None,
+                 faces_segm=None, faces_parents=None, ign_part_pairs=None, selfpen: Optional[dict] = None):
         dev = sdf.device
         self.device = dev
         f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=dev)
@@ -146,6 +147,27 @@ class ProxTemporalFitter:
                 raise ValueError(f'body_mask must be a bool [{V}] tensor on the device of the SDF')
             self.scan, self.scan_point_num, self.body_mask = scan.detach().contiguous(), scan_point_num.contiguous(), body_mask.contiguous()
             self._scan_faces = torch.from_numpy(np.ascontiguousarray(self.body_model.faces, np.int32)).to(dev)     # uploaded once
+        # self-penetration (fitting_temp_slide.py:618-635, `interpenetration: True`): the part segmentation of the faces (optional, as
+        # FilterFaces takes it) and `selfpen` = dict(sigma, penalize_outside, max_pairs); active only with a positive
+        # weights['coll_loss_weight'] (default 0).  The tables are uploaded here, once.
+        sp = dict(selfpen or {})
+        unknown = set(sp) - {'sigma', 'penalize_outside', 'max_pairs'}
+        if unknown:
+            raise ValueError(f'selfpen: unknown keys {sorted(unknown)} (sigma, penalize_outside, max_pairs)')
+        from . import selfpen as _sp
+        self._sp_cfg = dict(sigma=_sp._sigma(sp.get('sigma', 1e-4)), penalize_outside=bool(sp.get('penalize_outside', True)),
+                            max_pairs=int(sp.get('max_pairs', _sp.DEFAULT_MAX_PAIRS)))
+        if self._sp_cfg['max_pairs'] < 1:
+            raise ValueError('selfpen: max_pairs must be at least 1')
+        if (faces_parents is not None or ign_part_pairs is not None) and faces_segm is None:
+            raise ValueError('faces_parents / ign_part_pairs need faces_segm')
+        lib_ = self.body_model._lib_override or (_hip.get_lib() if dev.type == 'cuda' else None)
+        self._sp_tables = None
+        if lib_ is not None:
+            nF = int(np.asarray(self.body_model.faces).shape[0])
+            self._sp_tables = (torch.from_numpy(np.ascontiguousarray(self.body_model.faces, np.int32)).to(dev),
+                               _sp._per_face(lib_, faces_segm, nF, dev, 'faces_segm'), _sp._per_face(lib_, faces_parents, nF, dev, 'faces_parents'),
+                               _sp._ign(lib_, ign_part_pairs, dev)[0])
         self.params = [p for n, p in self.body_model.named_parameters() if p.requires_grad] + [self.pose_embedding]
         # optim_factory.py:43-46.  capturable: the step count lives on the device so that a captured step can be replayed
         self.optimizer = torch.optim.Adam(self.params, lr=lr, capturable=self.pose_embedding.is_cuda)
@@ -248,8 +270,28 @@ class ProxTemporalFitter:
                                             w.get('m2s_weight', 0), w.get('rho_s2m', 1), w.get('rho_m2s', 1), check_counts=False,
                                             _lib=bm._lib_override)
             total = total + (s2m_dist + m2s_dist)
-        return dict(total_loss=total, joint_loss=joint_loss, s2m_dist=s2m_dist, m2s_dist=m2s_dist, self_penetration_loss=zero,
-                    sdf_penetration_loss=sdf_pen, contact_loss=contact_loss, smooth_acc_loss=zero, smooth_vel_loss=zero,
+        # ---- self-penetration (:618-635) on the camera-space vertices; the search runs on the detached vertices
+        pen_loss = zero
+        if w.get('coll_loss_weight', 0) > 0:
+            from .selfpen import self_penetration_term
+            if self._sp_tables is None:
+                raise _hip.LemoHipError('the self-penetration term needs tensors on a HIP device (no CPU fallback)')
+            fc, segm, par, ign = self._sp_tables
+            pen_loss = self_penetration_term(verts, fc, w['coll_loss_weight'], segm, par, ign, _lib=bm._lib_override, **self._sp_cfg)
+            total = total + pen_loss
+        # ---- marker acceleration / velocity (:756-772) on the camera-space vertices
+        smooth_acc, smooth_vel = zero, zero
+        if w.get('smooth_acc_weight', 0) > 0 or w.get('smooth_vel_weight', 0) > 0:
+            mk = verts[:, self.ids['markers81'], :]
+            mvel = mk[1:] - mk[0:-1]
+            if w.get('smooth_acc_weight', 0) > 0:
+                smooth_acc = torch.mean((mvel[1:] - mvel[0:-1]) ** 2) * w['smooth_acc_weight']
+                total = total + smooth_acc
+            if w.get('smooth_vel_weight', 0) > 0:
+                smooth_vel = torch.mean(mvel ** 2) * w['smooth_vel_weight']
+                total = total + smooth_vel
+        return dict(total_loss=total, joint_loss=joint_loss, s2m_dist=s2m_dist, m2s_dist=m2s_dist, self_penetration_loss=pen_loss,
+                    sdf_penetration_loss=sdf_pen, contact_loss=contact_loss, smooth_acc_loss=smooth_acc, smooth_vel_loss=smooth_vel,
                     motion_prior_smooth_loss=smooth, loss_fric_tangent=fric_t, loss_fric_normal=fric_n,
                     motion_infill_loss=infill, motion_infill_contact_loss=infill_contact)
 
