@@ -941,6 +941,31 @@ int lemo_selfpen_loss_forward(const float* verts, int B, int V, const int* faces
 int lemo_selfpen_loss_backward(const float* verts, int B, int V, const int* faces, int F, const int* pairs, int C, const int* count, float sigma,
                                int penalize_outside, const float* gloss, float* gverts, void* stream);
 
+/* ---- scene signed-distance volume (csrc/scene_sdf_kernels.hip): a triangle mesh -> the sdf / grid_min / grid_max that lemo_sdf_sample, the
+ * PROX engine and ProxTemporalFitter take.  The definition is this project's (that file's header states it in full); the program that
+ * made PROX's own <scene>_sdf.npy was never published ----
+ * verts [V][3] fp32, faces [F][3] int32.  Tables, built once per mesh by the caller (float64, rounded to fp32): face_n [F][3] unit face
+ * normals, ALL ZERO for a triangle to be ignored (zero area); edge_n [F][3][3]: for edge e of face f (0: v0 v1, 1: v1 v2, 2: v2 v0) the
+ * sum of the unit normals of the faces sharing that undirected edge; vert_n [V][3]: the incident faces' unit normals weighted by their
+ * corner angles.  A triangle with a vertex index outside [0, V) or a coordinate that is not finite is ignored as well.
+ * gmin, gmax: host float[3], finite, gmin < gmax.  Out: sdf [D][H][W] (x, y, z) at the voxel centres gmin + (i + 0.5) (gmax - gmin) / dim:
+ * the exact distance to the nearest point of the mesh, negative where (p - c) . n < 0 for the closest point c and the pseudonormal n
+ * of the feature it lies on; +inf everywhere without a valid triangle.  nearest (or NULL) [D][H][W]: the winning face (smallest squared
+ * distance, then lowest index; -1 without one).  mode: LEMO_SCENE_SDF_BRUTE streams every triangle past every voxel,
+ * LEMO_SCENE_SDF_GRID searches a grid^3 cell grid outward (grid 0 = max(D, H, W) / 8 clamped to 2 .. 32, else 2 .. 32),
+ * LEMO_SCENE_SDF_AUTO is GRID except for tiny meshes; the output does not depend on mode or grid, bit for bit, and repeated runs are
+ * bit-identical.  ws: lemo_scene_sdf_ws_bytes(F, D, H, W, mode, grid) bytes of device scratch (0 for brute force: ws may be NULL).
+ * No allocation, no host synchronisation, capturable in a graph.
+ * LEMO_ERR_SHAPE: F, V, D, H or W < 1, a side > 1024, D H W > 2^28, F > 2^22, V > 2^24; LEMO_ERR_ARG: null pointers, an unknown mode or
+ * grid, bounds that are not finite or empty, a workspace that is too small.  Nothing is launched then. */
+#define LEMO_SCENE_SDF_AUTO 0
+#define LEMO_SCENE_SDF_BRUTE 1
+#define LEMO_SCENE_SDF_GRID 2
+long long lemo_scene_sdf_ws_bytes(int F, int D, int H, int W, int mode, int grid);               /* -1 for arguments the launch refuses */
+int lemo_scene_sdf_build(const float* verts, int V, const int* faces, int F, const float* face_n, const float* edge_n, const float* vert_n,
+                         const float* gmin, const float* gmax, int D, int H, int W, int mode, int grid, float* sdf, int* nearest, void* ws,
+                         long long ws_bytes, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

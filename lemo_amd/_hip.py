@@ -363,6 +363,9 @@ _SIGS = {
     'lemo_selfpen_search': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_longlong, vp]),
     'lemo_selfpen_loss_forward': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, vp]),
     'lemo_selfpen_loss_backward': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, vp, vp]),
+    'lemo_scene_sdf_ws_bytes': (C.c_longlong, [C.c_int] * 6),
+    'lemo_scene_sdf_build': (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)] + [C.c_int] * 5 +
+                             [vp, vp, vp, C.c_longlong, vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
