@@ -33,6 +33,7 @@
 //           offset + rank goes to scan[b][offset + rank] while that is below S.  The same launch writes rows scan_point_num[b] .. S - 1
 //           as zeros, so the output needs no initialisation.
 // Memory-bound: pass A and C each read the depth (2 or 4 B), the ray (8 B) and, with mask_on_color, one gathered mask byte per pixel.
+#include "geom_device.hpp"
 #include "kernels.hpp"
 
 #include <cmath>
@@ -57,8 +58,6 @@ struct DsParams {
 
 struct DsPix { float p[3], pc[3]; bool valid; };
 
-__device__ __forceinline__ float ds_dot3(float a0, float a1, float a2, float b0, float b1, float b2) { return fmaf(a2, b2, fmaf(a1, b1, a0 * b0)); }
-
 // depth of pixel (v, u) of the frame at `frame` (an element offset), before the depth-resolution mask
 __device__ __forceinline__ float ds_depth(const void* __restrict__ depth, size_t frame, int W, int v, int u, const DsParams& P) {
   const size_t at = frame + (size_t)v * W + (P.flip ? W - 1 - u : u);
@@ -68,9 +67,12 @@ __device__ __forceinline__ float ds_depth(const void* __restrict__ depth, size_t
 
 // p = ((x d, y d, d) - t_d) . R_d
 __device__ __forceinline__ void ds_unproject(float x, float y, float d, const DsParams& P, float p[3]) {
-  const float c0 = fmaf(x, d, -P.td[0]), c1 = fmaf(y, d, -P.td[1]), c2 = d - P.td[2];
+  const float c[3] = {fmaf(x, d, -P.td[0]), fmaf(y, d, -P.td[1]), d - P.td[2]};
 #pragma unroll
-  for (int j = 0; j < 3; ++j) p[j] = ds_dot3(c0, c1, c2, P.Rd[j], P.Rd[3 + j], P.Rd[6 + j]);
+  for (int j = 0; j < 3; ++j) {
+    const float col[3] = {P.Rd[j], P.Rd[3 + j], P.Rd[6 + j]};
+    p[j] = dot3(c, col);
+  }
 }
 
 // i: pixel of the frame (< H W); mask: this frame's mask (colour-sized or depth-sized, by the branch)

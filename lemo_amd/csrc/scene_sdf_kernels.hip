@@ -42,6 +42,7 @@
 //   16 times the error estimate (about 50 ulp of M = 2^-18 M), so a triangle that could win, or tie and win on its index, is never
 //   skipped.  GRID therefore equals BRUTE bit for bit, the nearest-face volume included, for every G.
 // AUTO: see SDF_AUTO_FACES below.  No allocation (caller's workspace), no host synchronisation, capturable in a graph.
+#include "geom_device.hpp"
 #include "kernels.hpp"
 
 #include <algorithm>
@@ -60,13 +61,10 @@ namespace lemo {
 #define SDF_HDR 16                                           // words of the workspace header: [0] big triangles, [1] bits of max |coordinate|
 #define SDF_TW 10                                            // words of a stored triangle
 #define SDF_TASKS 128                                        // shell rows examined per round: at most two segments each
-#define SDF_FMAX 3.0e38f
 #define SDF_CHEB_INF (1 << 20)
 
 struct SdfGeom { float g0[3], step[3]; int dim[3]; };
 struct SdfMesh { const float* verts; int V; const int* faces; int F; const float* face_n; };
-
-__device__ __forceinline__ float sdf_dot(const float x[3], const float y[3]) { return fmaf(x[2], y[2], fmaf(x[1], y[1], x[0] * y[0])); }
 
 // Ericson's closest point by Voronoi region, for p against the triangle (a, a + ab, a + ac) -> d^2; q = p - c;
 // feat: 0 face, 1 .. 3 edge v0 v1 / v1 v2 / v2 v0, 4 .. 6 vertex v0 / v1 / v2.  The regions are tested in Ericson's order (the
@@ -75,7 +73,7 @@ __device__ __forceinline__ float sdf_closest(const float p[3], const float a[3],
   float ap[3], bp[3], cp[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) { ap[k] = p[k] - a[k]; bp[k] = ap[k] - ab[k]; cp[k] = ap[k] - ac[k]; }
-  const float d1 = sdf_dot(ab, ap), d2 = sdf_dot(ac, ap), d3 = sdf_dot(ab, bp), d4 = sdf_dot(ac, bp), d5 = sdf_dot(ab, cp), d6 = sdf_dot(ac, cp);
+  const float d1 = dot3(ab, ap), d2 = dot3(ac, ap), d3 = dot3(ab, bp), d4 = dot3(ac, bp), d5 = dot3(ab, cp), d6 = dot3(ac, cp);
   const float vc = fmaf(d1, d4, -(d3 * d2)), vb = fmaf(d5, d2, -(d1 * d6)), va = fmaf(d3, d6, -(d5 * d4));
   const float e43 = d4 - d3, e56 = d5 - d6;
   float ns = vb, nt = vc, dn = va + vb + vc;
@@ -90,22 +88,15 @@ __device__ __forceinline__ float sdf_closest(const float p[3], const float a[3],
 #pragma unroll
   for (int k = 0; k < 3; ++k) q[k] = fmaf(-t, ac[k], fmaf(-s, ab[k], ap[k]));
   feat = ft;
-  return sdf_dot(q, q);
+  return dot3(q, q);
 }
 
 // face f -> the ten stored words (a, b - a, c - a, index); false: ignored (out[9] = -1)
 __device__ __forceinline__ bool sdf_tri_load(const SdfMesh& m, int f, float out[SDF_TW], float lo[3], float hi[3]) {
   int id[3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { id[k] = m.faces[3 * (size_t)f + k]; ok = ok && (unsigned)id[k] < (unsigned)m.V; }
   float c[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int i = ok ? id[k] : 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { c[k][a] = m.verts[3 * (size_t)i + a]; ok = ok && fabsf(c[k][a]) < SDF_FMAX; }
-  }
+  const bool ids = face_ids(m.faces, f, m.V, id);
+  bool ok = face_corners(m.verts, id, ids, c);
   const float n0 = m.face_n[3 * (size_t)f], n1 = m.face_n[3 * (size_t)f + 1], n2 = m.face_n[3 * (size_t)f + 2];
   ok = ok && (n0 != 0.f || n1 != 0.f || n2 != 0.f);
 #pragma unroll
@@ -190,7 +181,7 @@ __device__ __forceinline__ void sdf_finish(const SdfMesh& m, const float* __rest
                                             : vert_n + 3 * (size_t)m.faces[3 * (size_t)bf + (ft - 4)];
     const float n[3] = {np[0], np[1], np[2]};
     const float d = sqrtf(d2);
-    val = sdf_dot(q, n) < 0.f ? -d : d;
+    val = dot3(q, n) < 0.f ? -d : d;
   }
   sdf[o] = val;
   if (nearest) nearest[o] = bf;
@@ -210,12 +201,6 @@ __global__ void __launch_bounds__(SDF_BLOCK) sdf_brute_kernel(SdfMesh m, const f
 }
 
 // ---- grid ------------------------------------------------------------------------------------------------------------------------
-// cell of a coordinate: monotone non-decreasing in x, clamped to the grid
-__device__ __forceinline__ int sdf_cell(float x, float x0, float sx, int G) {
-  const float r = (x - x0) * sx;
-  return (int)fminf(fmaxf(r, 0.0f), (float)(G - 1));
-}
-
 struct SdfGrid { int G; float x0[3], sx[3], h[3]; };      // sx = G / extent, h = extent / G
 
 // workspace words: hdr [SDF_HDR], cnt [nc], cell_start [nc + 1], cursor [nc], cheb_a [nc], cheb_b [nc], tri [F][SDF_TW]
@@ -234,8 +219,8 @@ __device__ __forceinline__ int sdf_tri_cell(const SdfGrid& gr, const float lo[3]
   bool small = true;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    c[a] = sdf_cell(lo[a], gr.x0[a], gr.sx[a], gr.G);
-    small = small && sdf_cell(hi[a], gr.x0[a], gr.sx[a], gr.G) - c[a] <= 1;
+    c[a] = grid_cell(lo[a], gr.x0[a], gr.sx[a], gr.G);
+    small = small && grid_cell(hi[a], gr.x0[a], gr.sx[a], gr.G) - c[a] <= 1;
   }
   return small ? (c[2] * gr.G + c[1]) * gr.G + c[0] : -1;
 }
@@ -265,20 +250,8 @@ __global__ void __launch_bounds__(SDF_BLOCK) sdf_bin_kernel(SdfMesh m, SdfGrid g
 // exclusive scan of the nc <= 32768 counters (one workgroup): cell_start, and the fill cursors
 __global__ void __launch_bounds__(SDF_BLOCK) sdf_scan_kernel(int nc, SdfWs w) {
   __shared__ int s_part[SDF_BLOCK];
-  const int tid = threadIdx.x;
-  const int per = (nc + SDF_BLOCK - 1) / SDF_BLOCK, lo = min(tid * per, nc), hi = min(lo + per, nc);
-  int run = 0;
-  for (int k = lo; k < hi; ++k) run += w.cnt[k];
-  s_part[tid] = run;
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int k = 0; k < SDF_BLOCK; ++k) { const int v = s_part[k]; s_part[k] = acc; acc += v; }
-    w.cell_start[nc] = acc;
-  }
-  __syncthreads();
-  int acc = s_part[tid];
-  for (int k = lo; k < hi; ++k) { const int v = w.cnt[k]; w.cell_start[k] = acc; w.cursor[k] = acc; acc += v; }
+  const int total = block_exclusive_scan<SDF_BLOCK>(nc, s_part, [&](int k) { return w.cnt[k]; }, [&](int k, int acc) { w.cell_start[k] = acc; w.cursor[k] = acc; });
+  if (threadIdx.x == 0) w.cell_start[nc] = total;
 }
 
 // one separable pass of the Chebyshev distance transform along AXIS: out(c) = min over o on the line of max(|c - o|, in(o));
@@ -332,8 +305,8 @@ __global__ void __launch_bounds__(SDF_BLOCK) sdf_grid_kernel(SdfMesh m, const fl
   for (int a = 0; a < 3; ++a) {
     blo[a] = fmaf((float)b0[a] + 0.5f, g.step[a], g.g0[a]);
     bhi[a] = fmaf((float)min(b0[a] + bdim[a], g.dim[a]) - 0.5f, g.step[a], g.g0[a]);
-    bl[a] = sdf_cell(fminf(blo[a], bhi[a]), gr.x0[a], gr.sx[a], G);
-    bh[a] = sdf_cell(fmaxf(blo[a], bhi[a]), gr.x0[a], gr.sx[a], G);
+    bl[a] = grid_cell(fminf(blo[a], bhi[a]), gr.x0[a], gr.sx[a], G);
+    bh[a] = grid_cell(fmaxf(blo[a], bhi[a]), gr.x0[a], gr.sx[a], G);
     M = fmaxf(M, fmaxf(fabsf(gr.x0[a]), fabsf(gr.x0[a] + gr.h[a] * (float)G)));
   }
   const float slack = M * 0x1p-14f;

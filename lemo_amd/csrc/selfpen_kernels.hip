@@ -27,7 +27,7 @@
 //    frame at the PROX shape); the narrow phase runs behind it for the few pairs that survive.
 //    GRID: sp_bin_kernel (one workgroup per frame) bins every valid face by the cell of its box's MIN corner in a G x G x G grid over
 //    the frame's bounding box (counting sort in LDS, G <= 16: 16 KB of counters), and records K = the largest number of cells a box
-//    spans per axis.  sp_cell is monotone, so a face j whose box overlaps that of i has cell(min_j) in
+//    spans per axis.  grid_cell (geom_device.hpp) is monotone, so a face j whose box overlaps that of i has cell(min_j) in
 //    [cell(min_i) - K, cell(max_i)] on every axis: integer logic, exact, nothing is inflated by a tolerance.  The query visits those
 //    cells (the cells of one x-row are contiguous) and reads the candidates' boxes in cell order.
 // 2. Loss.  Triangle f = (p0, p1, p2): unit normal n, circumcentre o (barycentric form), circumradius r = abc / (2 |e1 x e2|).  Point v:
@@ -43,6 +43,7 @@
 //    triangle and shared by its three points; d/dp0 = -(d/dq1 + d/dq2 + sum d/dx).  Scatter by fp32 atomicAdd, as lemo_chamfer_backward.
 //    A zero-area triangle contributes nothing and receives nothing; an empty list gives L = 0 and a zero gradient without a host test.
 // AUTO: see SP_AUTO_MODE below.
+#include "geom_device.hpp"
 #include "kernels.hpp"
 
 #include <cmath>
@@ -55,40 +56,18 @@ namespace lemo {
 #define SP_GMAX 16                                           // largest (and default) grid side: G^3 counters in LDS
 #define SP_HDR 16                                            // 4-byte words of a frame's grid header
 #define SP_PMAX 64                                           // largest side of the ignore table
-#define SP_FMAX 3.0e38f
 
 struct SpFace { int id[3]; float p[3][3]; float lo[3], hi[3]; bool ok; };
 
-__device__ __forceinline__ void sp_cross(const float x[3], const float y[3], float o[3]) {
-  o[0] = fmaf(x[1], y[2], -(x[2] * y[1]));
-  o[1] = fmaf(x[2], y[0], -(x[0] * y[2]));
-  o[2] = fmaf(x[0], y[1], -(x[1] * y[0]));
-}
-__device__ __forceinline__ float sp_dot(const float x[3], const float y[3]) { return fmaf(x[2], y[2], fmaf(x[1], y[1], x[0] * y[0])); }
-
 // face f of the frame; not ok (an index outside [0, V), a coordinate that is not finite): an empty box, which overlaps nothing
 __device__ __forceinline__ void sp_face(const float* __restrict__ vf, int V, const int* __restrict__ faces, int f, SpFace& t) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    int i = faces[3 * (size_t)f + k];
-    ok = ok && (unsigned)i < (unsigned)V;
-    t.id[k] = i;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int i = ok ? t.id[k] : 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      t.p[k][a] = vf[3 * (size_t)i + a];
-      ok = ok && fabsf(t.p[k][a]) < SP_FMAX;
-    }
-  }
+  const bool ids = face_ids(faces, f, V, t.id);
+  const bool ok = face_corners(vf, t.id, ids, t.p);
   t.ok = ok;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    t.lo[a] = ok ? fminf(t.p[0][a], fminf(t.p[1][a], t.p[2][a])) : SP_FMAX;
-    t.hi[a] = ok ? fmaxf(t.p[0][a], fmaxf(t.p[1][a], t.p[2][a])) : -SP_FMAX;
+    t.lo[a] = ok ? fminf(t.p[0][a], fminf(t.p[1][a], t.p[2][a])) : GEOM_FMAX;
+    t.hi[a] = ok ? fmaxf(t.p[0][a], fmaxf(t.p[1][a], t.p[2][a])) : -GEOM_FMAX;
   }
 }
 
@@ -101,9 +80,9 @@ __device__ __forceinline__ bool sp_seg_tri(const float a[3], const float b[3], c
   const float d[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
   const float tv[3] = {a[0] - v0[0], a[1] - v0[1], a[2] - v0[2]};
   float pv[3], qv[3];
-  sp_cross(d, e2, pv);
-  sp_cross(tv, e1, qv);
-  const float det = sp_dot(e1, pv), U = sp_dot(tv, pv), W = sp_dot(d, qv), T = sp_dot(e2, qv), S = U + W;
+  cross3(d, e2, pv);
+  cross3(tv, e1, qv);
+  const float det = dot3(e1, pv), U = dot3(tv, pv), W = dot3(d, qv), T = dot3(e2, qv), S = U + W;
   const bool pos = det > 0.f && U >= 0.f && W >= 0.f && S <= det && T >= 0.f && T <= det;
   const bool neg = det < 0.f && U <= 0.f && W <= 0.f && S >= det && T <= 0.f && T >= det;
   return pos || neg;
@@ -150,6 +129,19 @@ __device__ __forceinline__ void sp_insert(int* __restrict__ pr, int m, int& fill
   pr[2 * k + 1] = j;
 }
 
+// A frame's workspace, laid out from `frame`: cnt [F], off [F]; GRID adds hdr [SP_HDR] ([0..2] x0, [3..5] scale as float bits,
+// [6..8] K), cell_start [G^3 + 1], item [F], box [F][6] (floats, in cell order).  P is a pointer to 4-byte words in the kernels, and
+// long long on the host, where laying a frame out from word 0 gives its size as `end`.
+template <typename P> struct SpWs { P cnt, off, hdr, cell_start, item, box, end; };
+template <typename P> __host__ __device__ inline SpWs<P> sp_ws(P frame, int F, int G, int mode) {
+  SpWs<P> w = {};
+  w.cnt = frame; w.off = w.cnt + F; w.end = w.off + F;
+  if (mode == LEMO_SELFPEN_GRID) {
+    w.hdr = w.end; w.cell_start = w.hdr + SP_HDR; w.item = w.cell_start + (G * G * G + 1); w.box = w.item + F; w.end = w.box + 6ll * F;
+  }
+  return w;
+}
+
 // what a thread of a fill pass owns: -> m (0: nothing to do)
 __device__ __forceinline__ int sp_slice(const int* __restrict__ cnt, const int* __restrict__ off, int i, int F, int C, int& base) {
   base = 0;
@@ -159,7 +151,7 @@ __device__ __forceinline__ int sp_slice(const int* __restrict__ cnt, const int* 
 }
 
 // ---- brute force -------------------------------------------------------------------------------------------------------------
-// grid (face block, frame).  ws per frame: cnt [F], off [F] (then the grid's part)
+// grid (face block, frame)
 template <bool FILL>
 __global__ void __launch_bounds__(SP_BLOCK) sp_brute_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F, SpSegm g,
                                                              int* __restrict__ ws, long long wstride, int* __restrict__ pairs, int C) {
@@ -167,11 +159,10 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_brute_kernel(const float* __restr
   __shared__ int s_any;
   const int tid = threadIdx.x, b = blockIdx.y, i = blockIdx.x * SP_BLOCK + tid;
   const float* __restrict__ vf = verts + (size_t)b * V * 3;
-  int* __restrict__ cnt = ws + (size_t)b * wstride;
-  const int* __restrict__ off = cnt + F;
+  const SpWs<int*> w = sp_ws(ws + (size_t)b * wstride, F, 0, LEMO_SELFPEN_BRUTE);
   int m = 0, base = 0, filled = 0, found = 0;
   if (FILL) {
-    m = sp_slice(cnt, off, i, F, C, base);
+    m = sp_slice(w.cnt, w.off, i, F, C, base);
     if (tid == 0) s_any = 0;
     __syncthreads();
     if (m > 0) s_any = 1;
@@ -185,7 +176,7 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_brute_kernel(const float* __restr
   } else {
     me.ok = false;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { me.lo[a] = SP_FMAX; me.hi[a] = -SP_FMAX; }
+    for (int a = 0; a < 3; ++a) { me.lo[a] = GEOM_FMAX; me.hi[a] = -GEOM_FMAX; }
   }
   const bool active = FILL ? m > 0 : true;
 
@@ -199,7 +190,7 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_brute_kernel(const float* __restr
       for (int a = 0; a < 3; ++a) { stage[a] = t.lo[a]; stage[3 + a] = t.hi[a]; }
     } else {
 #pragma unroll
-      for (int a = 0; a < 3; ++a) { stage[a] = SP_FMAX; stage[3 + a] = -SP_FMAX; }
+      for (int a = 0; a < 3; ++a) { stage[a] = GEOM_FMAX; stage[3 + a] = -GEOM_FMAX; }
     }
   };
   auto put = [&](int buf) {
@@ -231,51 +222,23 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_brute_kernel(const float* __restr
     if (more) put(buf ^ 1);
     __syncthreads();
   }
-  if (!FILL && i < F) cnt[i] = found;
+  if (!FILL && i < F) w.cnt[i] = found;
 }
 
 // ---- per-frame prefix sum ------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(SP_BLOCK) sp_scan_kernel(int F, int* __restrict__ ws, long long wstride, int* __restrict__ pairs, int C,
                                                             int* __restrict__ count) {
   __shared__ long long s_part[SP_BLOCK];
-  __shared__ long long s_total;
   const int tid = threadIdx.x, b = blockIdx.x;
-  const int* __restrict__ cnt = ws + (size_t)b * wstride;
-  int* __restrict__ off = ws + (size_t)b * wstride + F;
-  const int per = (F + SP_BLOCK - 1) / SP_BLOCK, lo = min(tid * per, F), hi = min(lo + per, F);
-  long long run = 0;
-  for (int k = lo; k < hi; ++k) run += cnt[k];
-  s_part[tid] = run;
-  __syncthreads();
-  if (tid == 0) {
-    long long acc = 0;
-    for (int k = 0; k < SP_BLOCK; ++k) { const long long v = s_part[k]; s_part[k] = acc; acc += v; }
-    s_total = acc;
-  }
-  __syncthreads();
-  long long acc = s_part[tid];
-  for (int k = lo; k < hi; ++k) { off[k] = (int)(acc < (long long)C ? acc : (long long)C); acc += cnt[k]; }
-  const long long total = s_total;
+  const SpWs<int*> w = sp_ws(ws + (size_t)b * wstride, F, 0, LEMO_SELFPEN_BRUTE);
+  const long long total = block_exclusive_scan<SP_BLOCK>(F, s_part, [&](int k) { return w.cnt[k]; },
+                                                         [&](int k, long long acc) { w.off[k] = (int)(acc < (long long)C ? acc : (long long)C); });
   if (tid == 0) count[b] = (int)(total < 2147483647ll ? total : 2147483647ll);
   int* __restrict__ pb = pairs + (size_t)b * C * 2;
   for (long long c = (total < (long long)C ? total : (long long)C) + tid; c < C; c += SP_BLOCK) { pb[2 * c] = -1; pb[2 * c + 1] = -1; }
 }
 
 // ---- grid ----------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned sp_key(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sp_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
-// cell of a coordinate: monotone non-decreasing in x for fixed (x0, sx)
-__device__ __forceinline__ int sp_cell(float x, float x0, float sx, int G) {
-  const float r = (x - x0) * sx;
-  return (int)fminf(fmaxf(r, 0.0f), (float)(G - 1));
-}
-
-// grid part of a frame's workspace: hdr [SP_HDR] ([0..2] x0, [3..5] scale as float bits, [6..8] K), cell_start [G^3 + 1], item [F],
-// box [F][6] in cell order
 __global__ void __launch_bounds__(SP_BLOCK) sp_bin_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F, int G,
                                                            int* __restrict__ ws, long long wstride) {
   __shared__ unsigned s_box[6];                                // max keys of hi[a] and of -lo[a]
@@ -284,10 +247,8 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_bin_kernel(const float* __restric
   __shared__ int s_part[SP_BLOCK];
   const int tid = threadIdx.x, b = blockIdx.x, nc = G * G * G;
   const float* __restrict__ vf = verts + (size_t)b * V * 3;
-  int* __restrict__ hdr = ws + (size_t)b * wstride + 2 * (size_t)F;
-  int* __restrict__ cell_start = hdr + SP_HDR;
-  int* __restrict__ item = cell_start + nc + 1;
-  float* __restrict__ box = reinterpret_cast<float*>(item + F);
+  const SpWs<int*> w = sp_ws(ws + (size_t)b * wstride, F, G, LEMO_SELFPEN_GRID);
+  float* __restrict__ box = reinterpret_cast<float*>(w.box);
   if (tid < 6) s_box[tid] = 0u;
   if (tid < 3) s_k[tid] = 0u;
   for (int k = tid; k < nc; k += SP_BLOCK) s_cnt[k] = 0;
@@ -299,7 +260,7 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_bin_kernel(const float* __restric
     sp_face(vf, V, faces, f, t);
     if (!t.ok) continue;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { kh[a] = max(kh[a], sp_key(t.hi[a])); kl[a] = max(kl[a], sp_key(-t.lo[a])); }
+    for (int a = 0; a < 3; ++a) { kh[a] = max(kh[a], float_key(t.hi[a])); kl[a] = max(kl[a], float_key(-t.lo[a])); }
   }
   if (kh[0]) {
 #pragma unroll
@@ -309,9 +270,9 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_bin_kernel(const float* __restric
   float x0[3], sx[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float hi = s_box[0] ? sp_unkey(s_box[a]) : 0.f, lo = s_box[0] ? -sp_unkey(s_box[3 + a]) : 0.f, e = hi - lo;
+    const float hi = s_box[0] ? float_unkey(s_box[a]) : 0.f, lo = s_box[0] ? -float_unkey(s_box[3 + a]) : 0.f, e = hi - lo;
     x0[a] = lo;
-    sx[a] = (e > 0.f && e < SP_FMAX) ? (float)G / e : 0.f;
+    sx[a] = (e > 0.f && e < GEOM_FMAX) ? (float)G / e : 0.f;
   }
 
   unsigned kk[3] = {0u, 0u, 0u};
@@ -322,8 +283,8 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_bin_kernel(const float* __restric
     int c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      c[a] = sp_cell(t.lo[a], x0[a], sx[a], G);
-      kk[a] = max(kk[a], (unsigned)(sp_cell(t.hi[a], x0[a], sx[a], G) - c[a]));
+      c[a] = grid_cell(t.lo[a], x0[a], sx[a], G);
+      kk[a] = max(kk[a], (unsigned)(grid_cell(t.hi[a], x0[a], sx[a], G) - c[a]));
     }
     atomicAdd(&s_cnt[(c[2] * G + c[1]) * G + c[0]], 1);
   }
@@ -332,22 +293,11 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_bin_kernel(const float* __restric
   __syncthreads();
   if (tid == 0) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) { hdr[a] = __float_as_int(x0[a]); hdr[3 + a] = __float_as_int(sx[a]); hdr[6 + a] = (int)s_k[a]; }
+    for (int a = 0; a < 3; ++a) { w.hdr[a] = __float_as_int(x0[a]); w.hdr[3 + a] = __float_as_int(sx[a]); w.hdr[6 + a] = (int)s_k[a]; }
   }
-  // exclusive scan of nc <= 4096 counters: a serial run of nc / 256 per thread, then the 256 run totals
-  const int per = (nc + SP_BLOCK - 1) / SP_BLOCK, lo = min(tid * per, nc), hi = min(lo + per, nc);
-  int run = 0;
-  for (int k = lo; k < hi; ++k) run += s_cnt[k];
-  s_part[tid] = run;
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int k = 0; k < SP_BLOCK; ++k) { const int v = s_part[k]; s_part[k] = acc; acc += v; }
-    cell_start[nc] = acc;                                      // the valid faces
-  }
-  __syncthreads();
-  int acc = s_part[tid];
-  for (int k = lo; k < hi; ++k) { const int v = s_cnt[k]; s_cnt[k] = acc; cell_start[k] = acc; acc += v; }   // s_cnt becomes the fill cursor
+  // exclusive scan of the nc <= 4096 counters; s_cnt becomes the fill cursor
+  const int valid = block_exclusive_scan<SP_BLOCK>(nc, s_part, [&](int k) { return s_cnt[k]; }, [&](int k, int acc) { s_cnt[k] = acc; w.cell_start[k] = acc; });
+  if (tid == 0) w.cell_start[nc] = valid;                      // the valid faces
   __syncthreads();
   for (int f = tid; f < F; f += SP_BLOCK) {
     SpFace t;
@@ -355,9 +305,9 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_bin_kernel(const float* __restric
     if (!t.ok) continue;
     int c[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = sp_cell(t.lo[a], x0[a], sx[a], G);
+    for (int a = 0; a < 3; ++a) c[a] = grid_cell(t.lo[a], x0[a], sx[a], G);
     const int slot = atomicAdd(&s_cnt[(c[2] * G + c[1]) * G + c[0]], 1);      // the order inside a cell is free: the fill pass sorts
-    item[slot] = f;
+    w.item[slot] = f;
 #pragma unroll
     for (int a = 0; a < 3; ++a) { box[6 * (size_t)slot + a] = t.lo[a]; box[6 * (size_t)slot + 3 + a] = t.hi[a]; }
   }
@@ -370,35 +320,30 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_grid_kernel(const float* __restri
   const int b = blockIdx.y, i = blockIdx.x * SP_BLOCK + threadIdx.x;
   if (i >= F) return;
   const float* __restrict__ vf = verts + (size_t)b * V * 3;
-  int* __restrict__ cnt = ws + (size_t)b * wstride;
-  const int* __restrict__ off = cnt + F;
+  const SpWs<int*> w = sp_ws(ws + (size_t)b * wstride, F, G, LEMO_SELFPEN_GRID);
   int m = 0, base = 0, filled = 0, found = 0;
   if (FILL) {
-    m = sp_slice(cnt, off, i, F, C, base);
+    m = sp_slice(w.cnt, w.off, i, F, C, base);
     if (m == 0) return;
   }
   int* __restrict__ pr = pairs + ((size_t)b * C + base) * 2;
-  const int nc = G * G * G;
-  const int* __restrict__ hdr = cnt + 2 * (size_t)F;
-  const int* __restrict__ cell_start = hdr + SP_HDR;
-  const int* __restrict__ item = cell_start + nc + 1;
-  const float* __restrict__ box = reinterpret_cast<const float*>(item + F);
+  const float* __restrict__ box = reinterpret_cast<const float*>(w.box);
   SpFace me;
   sp_face(vf, V, faces, i, me);
   if (me.ok) {
     int lc[3], hc[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const float x0 = __int_as_float(hdr[a]), sx = __int_as_float(hdr[3 + a]);
-      lc[a] = max(sp_cell(me.lo[a], x0, sx, G) - hdr[6 + a], 0);
-      hc[a] = sp_cell(me.hi[a], x0, sx, G);
+      const float x0 = __int_as_float(w.hdr[a]), sx = __int_as_float(w.hdr[3 + a]);
+      lc[a] = max(grid_cell(me.lo[a], x0, sx, G) - w.hdr[6 + a], 0);
+      hc[a] = grid_cell(me.hi[a], x0, sx, G);
     }
     for (int cz = lc[2]; cz <= hc[2]; ++cz)
       for (int cy = lc[1]; cy <= hc[1]; ++cy) {
         const int row = (cz * G + cy) * G;
-        const int s0 = cell_start[row + lc[0]], s1 = cell_start[row + hc[0] + 1];      // the cells of one x-row are contiguous
+        const int s0 = w.cell_start[row + lc[0]], s1 = w.cell_start[row + hc[0] + 1];      // the cells of one x-row are contiguous
         for (int s = s0; s < s1; ++s) {
-          const int j = item[s];
+          const int j = w.item[s];
           const float* __restrict__ bj = box + 6 * (size_t)s;
           if (j > i && sp_overlap(me.lo, me.hi, bj[0], bj[1], bj[2], bj[3], bj[4], bj[5])) {
             SpFace other;
@@ -410,7 +355,7 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_grid_kernel(const float* __restri
         }
       }
   }
-  if (!FILL) cnt[i] = found;
+  if (!FILL) w.cnt[i] = found;
 }
 
 // ---- the cone distance field ---------------------------------------------------------------------------------------------------
@@ -468,7 +413,7 @@ template <int N> __device__ __forceinline__ SpDual<N> operator*(const SpDual<N>&
 template <typename T> __device__ __forceinline__ bool sp_cone(const T q1[3], const T q2[3], T n[3], T o[3], T& r) {
   const T N0 = q1[1] * q2[2] - q1[2] * q2[1], N1 = q1[2] * q2[0] - q1[0] * q2[2], N2 = q1[0] * q2[1] - q1[1] * q2[0];
   const T A2sq = N0 * N0 + N1 * N1 + N2 * N2;
-  if (!(sp_val(A2sq) > 0.f) || !(sp_val(A2sq) < SP_FMAX)) return false;
+  if (!(sp_val(A2sq) > 0.f) || !(sp_val(A2sq) < GEOM_FMAX)) return false;
   const T A2 = sp_sqrt(A2sq);
   n[0] = N0 / A2; n[1] = N1 / A2; n[2] = N2 / A2;
   const T d0 = q1[0] - q2[0], d1 = q1[1] - q2[1], d2 = q1[2] - q2[2];
@@ -477,12 +422,12 @@ template <typename T> __device__ __forceinline__ bool sp_cone(const T q1[3], con
   const T c2 = q1[0] * q1[0] + q1[1] * q1[1] + q1[2] * q1[2];   // |p0 - p1|^2, opposite p2
   const T w0 = a2 * (b2 + c2 - a2), w1 = b2 * (c2 + a2 - b2), w2 = c2 * (a2 + b2 - c2);
   const T wsum = w0 + w1 + w2;
-  if (!(sp_val(wsum) > 0.f) || !(sp_val(wsum) < SP_FMAX)) return false;
+  if (!(sp_val(wsum) > 0.f) || !(sp_val(wsum) < GEOM_FMAX)) return false;
   const T u1 = w1 / wsum, u2 = w2 / wsum;                      // p0's weight multiplies the origin
 #pragma unroll
   for (int k = 0; k < 3; ++k) o[k] = u1 * q1[k] + u2 * q2[k];
   r = sp_sqrt(a2 * b2 * c2) / (A2 * 2.0f);
-  return sp_val(r) > 0.f && sp_val(r) < SP_FMAX;
+  return sp_val(r) > 0.f && sp_val(r) < GEOM_FMAX;
 }
 
 // Psi(n, o, r; x) and its partials: d Psi = c_h dh + c_rho drho + c_r dr with dh = n . dd + d . dn, drho = u . dd - h u . dn (u = q / rho,
@@ -606,7 +551,7 @@ __device__ __forceinline__ void sp_side_bwd(const SpTri& R, const SpTri& P, floa
     SpPsi s;
     sp_psi(nv, ov, r.v, x, sigma, outside, s);
     const float gp = 2.0f * s.psi * gl;
-    if (gp == 0.f || !(fabsf(gp) < SP_FMAX)) continue;
+    if (gp == 0.f || !(fabsf(gp) < GEOM_FMAX)) continue;
     any = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -667,9 +612,7 @@ int sp_list_shape(int B, int V, int F, int C) {
   return 0;
 }
 
-long long sp_words(int F, int mode, int G) {
-  return 2ll * F + (mode == LEMO_SELFPEN_GRID ? SP_HDR + (long long)G * G * G + 1 + 7ll * F : 0ll);
-}
+long long sp_words(int F, int mode, int G) { return sp_ws(0ll, F, G, mode).end; }
 
 // what `auto` means.  Decided by the run of tools/selfpen_rate.py recorded in profiles/selfpen_rate.txt (MI355X, B = 100, V = 10475,
 // F = 20908, arms pushed into the torso): brute force 32.8 ms, grid 16 77.9 ms, grid 8 100.0 ms.  The pushed arms stretch the triangles

@@ -39,7 +39,7 @@
 //     VIS_MARGIN on every side, and the predicate against the vertices binned there.  A hit is a plain store of 0 (idempotent).
 //   vis_big_kernel: triangles that cover more than VIS_BIG cells, and THIN ones, one workgroup per triangle against every vertex of
 //     the frame (depth_raster_big_kernel's scheme).
-// Why the inflation is conservative.  vis_cell is monotone in fp32 (a subtraction, a product, a truncation, a clamp), so every vertex
+// Why the inflation is conservative.  grid_cell is monotone in fp32 (geom_device.hpp), so every vertex
 // whose pi lies in the inflated box is in a visited cell, exactly.  What has to be covered is where the fp32 predicate can say "hit"
 // outside the exact projected triangle.  U, V and det - U - V are the edge functions det[w, P_i, P_j] = w_z P_iz P_jz x (twice the
 // signed area of (pi, pi_i, pi_j)); each carries an absolute error of about 2^-20 |w| |P| |e| (two roundings per cross-product term,
@@ -51,6 +51,7 @@
 // estimate with a wide margin, not a proof to the last constant.  Thin projections (edge-on triangles, slivers) have no bound at all --
 // on an exactly edge-on triangle every quantity is rounding noise along the whole extended line -- so they are tested against every
 // vertex, like the large ones.  The tests hold brute force and binned to equality on every bit.
+#include "geom_device.hpp"
 #include "kernels.hpp"
 
 #include <cmath>
@@ -78,7 +79,7 @@ struct VisTri { float nd[3], a[3], q[3], p0[3], tn; };
 __device__ __forceinline__ bool vis_ray(const float p[3], const float c[3], float min_dist, float w[3]) {
   const float dx = c[0] - p[0], dy = c[1] - p[1], dz = c[2] - p[2];
   const float len = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx)));
-  if (!(len > min_dist) || !(len < 3.0e38f)) { w[0] = 0.f; w[1] = 0.f; w[2] = 0.f; return false; }
+  if (!(len > min_dist) || !(len < GEOM_FMAX)) { w[0] = 0.f; w[1] = 0.f; w[2] = 0.f; return false; }
   const float s = min_dist / len;
   w[0] = fmaf(s, dx, p[0]) - c[0];
   w[1] = fmaf(s, dy, p[1]) - c[1];
@@ -86,28 +87,21 @@ __device__ __forceinline__ bool vis_ray(const float p[3], const float c[3], floa
   return true;
 }
 
-__device__ __forceinline__ void vis_cross(const float x[3], const float y[3], float o[3]) {
-  o[0] = fmaf(x[1], y[2], -(x[2] * y[1]));
-  o[1] = fmaf(x[2], y[0], -(x[0] * y[2]));
-  o[2] = fmaf(x[0], y[1], -(x[1] * y[0]));
-}
-__device__ __forceinline__ float vis_dot(const float x[3], const float y[3]) { return fmaf(x[2], y[2], fmaf(x[1], y[1], x[0] * y[0])); }
-
 // P_k = v_k - c (already subtracted by the caller with vis_rel) -> the triangle's three vectors and scalar
 __device__ __forceinline__ void vis_tri(const float P0[3], const float P1[3], const float P2[3], VisTri& t) {
   float e1[3], e2[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) { e1[k] = P1[k] - P0[k]; e2[k] = P2[k] - P0[k]; }
-  vis_cross(e2, e1, t.nd);
-  vis_cross(P0, e2, t.a);
-  vis_cross(e1, P0, t.q);
-  t.tn = vis_dot(P0, t.nd);
+  cross3(e2, e1, t.nd);
+  cross3(P0, e2, t.a);
+  cross3(e1, P0, t.q);
+  t.tn = dot3(P0, t.nd);
 #pragma unroll
   for (int k = 0; k < 3; ++k) t.p0[k] = P0[k];
 }
 
 __device__ __forceinline__ bool vis_hit(const float w[3], const float nd[3], const float a[3], const float q[3], const float p0[3], float tn) {
-  const float det = vis_dot(w, nd), U = vis_dot(w, a), V = vis_dot(w, q), S = U + V;
+  const float det = dot3(w, nd), U = dot3(w, a), V = dot3(w, q), S = U + V;
   const float r0 = p0[0] - w[0], r1 = p0[1] - w[1], r2 = p0[2] - w[2];
   const float m = fmaf(r2, nd[2], fmaf(r1, nd[1], r0 * nd[0]));
   const bool pos = det > 0.f && U >= 0.f && V >= 0.f && S <= det && tn >= 0.f && m <= 0.f;
@@ -122,9 +116,9 @@ __device__ __forceinline__ void vis_rel(const float* __restrict__ v, const float
 // face f of the frame -> setup; a face that names a vertex outside [0, V) never hits (all zeros: det == 0)
 __device__ __forceinline__ bool vis_face(const float* __restrict__ vf, int V, const int* __restrict__ faces, int f, const float c[3],
                                          float P0[3], float P1[3], float P2[3], VisTri& t) {
-  int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
-  const bool ok = (unsigned)i0 < (unsigned)V && (unsigned)i1 < (unsigned)V && (unsigned)i2 < (unsigned)V;
-  i0 = ok ? i0 : 0; i1 = ok ? i1 : 0; i2 = ok ? i2 : 0;       // (vertex 0, vertex 0, vertex 0): degenerate, nd = a = q = 0, det == 0
+  int id[3];
+  const bool ok = face_ids(faces, f, V, id);
+  const int i0 = ok ? id[0] : 0, i1 = ok ? id[1] : 0, i2 = ok ? id[2] : 0;      // (vertex 0, vertex 0, vertex 0): degenerate, nd = a = q = 0, det == 0
   vis_rel(vf + 3 * (size_t)i0, c, P0);
   vis_rel(vf + 3 * (size_t)i1, c, P1);
   vis_rel(vf + 3 * (size_t)i2, c, P2);
@@ -209,21 +203,17 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_brute_kernel(const float* __res
 }
 
 // ---- binned ------------------------------------------------------------------------------------------------------------------
-// order-preserving key of a float (NaN never reaches here)
-__device__ __forceinline__ unsigned vis_key(float x) {
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float vis_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
-// cell of a projected coordinate: monotone non-decreasing in x for fixed (x0, sx)
-__device__ __forceinline__ int vis_cell(float x, float x0, float sx, int G) {
-  const float r = (x - x0) * sx;
-  return (int)fminf(fmaxf(r, 0.0f), (float)(G - 1));
+// A frame's workspace, laid out from `frame`: hdr [VIS_HDR] ([0] 1 = binned, 0 = brute force; [1..4] x0, y0, sx, sy as float bits),
+// cell_start [G G + 1], items [V], wdir [V][3] (floats, in cell order).  P is a pointer to 4-byte words in the kernels, and long long on
+// the host, where laying a frame out from word 0 gives its size as `end`.
+template <typename P> struct VisWs { P hdr, cell_start, items, wdir, end; };
+template <typename P> __host__ __device__ inline VisWs<P> vis_ws(P frame, int V, int G) {
+  VisWs<P> w;
+  w.hdr = frame; w.cell_start = w.hdr + VIS_HDR; w.items = w.cell_start + (G * G + 1); w.wdir = w.items + V; w.end = w.wdir + 3ll * V;
+  return w;
 }
 
-// frame header: [0] 1 = binned, 0 = brute force; [1..4] x0, y0, sx, sy as float bits; ws per frame: hdr, cell_start [G G + 1], cell_items
-// [V], wdir [V][3]
+// the bins of every frame (NaN never reaches float_key: a vertex that cannot be projected sends the frame to brute force first)
 __global__ void __launch_bounds__(VIS_BLOCK) vis_bin_kernel(const float* __restrict__ verts, int V, const float* __restrict__ cam, float min_dist,
                                                             int G, int* __restrict__ ws, long long wstride) {
   __shared__ unsigned s_box[5];                                // max keys of x, -x, y, -y; [4]: a vertex that cannot be projected
@@ -231,10 +221,9 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_bin_kernel(const float* __restr
   __shared__ int s_part[VIS_BLOCK];
   const int tid = threadIdx.x, b = blockIdx.x, nc = G * G;
   const float* __restrict__ vf = verts + (size_t)b * V * 3;
-  int* __restrict__ hdr = ws + (size_t)b * wstride;
-  int* __restrict__ cell_start = hdr + VIS_HDR;
-  int* __restrict__ items = cell_start + nc + 1;
-  float* __restrict__ wdir = reinterpret_cast<float*>(items + V);
+  const VisWs<int*> fr = vis_ws(ws + (size_t)b * wstride, V, G);
+  int* __restrict__ hdr = fr.hdr;
+  float* __restrict__ wdir = reinterpret_cast<float*>(fr.wdir);
   float c[3];
   vis_cam(cam, b, c);
   if (tid < 5) s_box[tid] = 0u;
@@ -247,8 +236,8 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_bin_kernel(const float* __restr
     vis_rel(vf + 3 * (size_t)i, c, P);
     const float x = P[0] / P[2], y = P[1] / P[2];
     if (!(P[2] >= VIS_ZMIN) || !(fabsf(x) <= VIS_FOV) || !(fabsf(y) <= VIS_FOV)) { bad = 1u; continue; }
-    kx1 = max(kx1, vis_key(x)); kx0 = max(kx0, vis_key(-x));
-    ky1 = max(ky1, vis_key(y)); ky0 = max(ky0, vis_key(-y));
+    kx1 = max(kx1, float_key(x)); kx0 = max(kx0, float_key(-x));
+    ky1 = max(ky1, float_key(y)); ky0 = max(ky0, float_key(-y));
   }
   if (kx1) { atomicMax(&s_box[0], kx1); atomicMax(&s_box[1], kx0); atomicMax(&s_box[2], ky1); atomicMax(&s_box[3], ky0); }
   if (bad) atomicMax(&s_box[4], 1u);
@@ -257,7 +246,7 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_bin_kernel(const float* __restr
     if (tid == 0) hdr[0] = 0;
     return;
   }
-  const float x1 = vis_unkey(s_box[0]), x0 = -vis_unkey(s_box[1]), y1 = vis_unkey(s_box[2]), y0 = -vis_unkey(s_box[3]);
+  const float x1 = float_unkey(s_box[0]), x0 = -float_unkey(s_box[1]), y1 = float_unkey(s_box[2]), y0 = -float_unkey(s_box[3]);
   const float ex = x1 - x0, ey = y1 - y0;
   const float sx = ex > 0.f ? (float)G / ex : 0.f, sy = ey > 0.f ? (float)G / ey : 0.f;
   if (tid == 0) {
@@ -268,33 +257,22 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_bin_kernel(const float* __restr
   for (int i = tid; i < V; i += VIS_BLOCK) {
     float P[3];
     vis_rel(vf + 3 * (size_t)i, c, P);
-    const int cell = vis_cell(P[1] / P[2], y0, sy, G) * G + vis_cell(P[0] / P[2], x0, sx, G);
+    const int cell = grid_cell(P[1] / P[2], y0, sy, G) * G + grid_cell(P[0] / P[2], x0, sx, G);
     atomicAdd(&s_cnt[cell], 1);
   }
   __syncthreads();
-  // exclusive scan of nc <= 4096 counters: a serial run of nc / 256 per thread, then the 256 run totals
-  const int per = (nc + VIS_BLOCK - 1) / VIS_BLOCK, lo = min(tid * per, nc), hi = min(lo + per, nc);
-  int run = 0;
-  for (int k = lo; k < hi; ++k) run += s_cnt[k];
-  s_part[tid] = run;
-  __syncthreads();
-  if (tid == 0) {
-    int acc = 0;
-    for (int k = 0; k < VIS_BLOCK; ++k) { const int v = s_part[k]; s_part[k] = acc; acc += v; }
-  }
-  __syncthreads();
-  int acc = s_part[tid];
-  for (int k = lo; k < hi; ++k) { const int v = s_cnt[k]; s_cnt[k] = acc; cell_start[k] = acc; acc += v; }   // s_cnt becomes the fill cursor
-  if (tid == 0) cell_start[nc] = V;
+  // exclusive scan of the nc <= 4096 counters; s_cnt becomes the fill cursor
+  block_exclusive_scan<VIS_BLOCK>(nc, s_part, [&](int k) { return s_cnt[k]; }, [&](int k, int acc) { s_cnt[k] = acc; fr.cell_start[k] = acc; });
+  if (tid == 0) fr.cell_start[nc] = V;
   __syncthreads();
   for (int i = tid; i < V; i += VIS_BLOCK) {
     float P[3], w[3];
     const float p[3] = {vf[3 * (size_t)i], vf[3 * (size_t)i + 1], vf[3 * (size_t)i + 2]};
     vis_rel(p, c, P);
-    const int cell = vis_cell(P[1] / P[2], y0, sy, G) * G + vis_cell(P[0] / P[2], x0, sx, G);
+    const int cell = grid_cell(P[1] / P[2], y0, sy, G) * G + grid_cell(P[0] / P[2], x0, sx, G);
     const int slot = atomicAdd(&s_cnt[cell], 1);
     vis_ray(p, c, min_dist, w);
-    items[slot] = i;
+    fr.items[slot] = i;
     wdir[3 * (size_t)slot] = w[0]; wdir[3 * (size_t)slot + 1] = w[1]; wdir[3 * (size_t)slot + 2] = w[2];
   }
 }
@@ -307,8 +285,8 @@ __device__ __forceinline__ void vis_box(const float P0[3], const float P1[3], co
   const float ax = P0[0] / P0[2], ay = P0[1] / P0[2], bx = P1[0] / P1[2], by = P1[1] / P1[2], cx = P2[0] / P2[2], cy = P2[1] / P2[2];
   const float xmin = fminf(ax, fminf(bx, cx)), xmax = fmaxf(ax, fmaxf(bx, cx));
   const float ymin = fminf(ay, fminf(by, cy)), ymax = fmaxf(ay, fmaxf(by, cy));
-  o.lx = vis_cell(xmin - VIS_MARGIN, x0, sx, G); o.hx = vis_cell(xmax + VIS_MARGIN, x0, sx, G);
-  o.ly = vis_cell(ymin - VIS_MARGIN, y0, sy, G); o.hy = vis_cell(ymax + VIS_MARGIN, y0, sy, G);
+  o.lx = grid_cell(xmin - VIS_MARGIN, x0, sx, G); o.hx = grid_cell(xmax + VIS_MARGIN, x0, sx, G);
+  o.ly = grid_cell(ymin - VIS_MARGIN, y0, sy, G); o.hy = grid_cell(ymax + VIS_MARGIN, y0, sy, G);
   const float side = fmaxf(xmax - xmin, ymax - ymin);
   const float area2 = fabsf(fmaf(bx - ax, cy - ay, -((cx - ax) * (by - ay))));
   const bool thin = !(area2 >= VIS_THIN * (side * side));      // also a projection that is not finite
@@ -320,12 +298,10 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_tri_kernel(const float* __restr
                                                             const float* __restrict__ cam, int G, const int* __restrict__ ws, long long wstride,
                                                             unsigned char* __restrict__ vis) {
   const int b = blockIdx.y, f = blockIdx.x * VIS_BLOCK + threadIdx.x;
-  const int* __restrict__ hdr = ws + (size_t)b * wstride;
+  const VisWs<const int*> fr = vis_ws(ws + (size_t)b * wstride, V, G);
+  const int* __restrict__ hdr = fr.hdr;
   if (hdr[0] != 1 || f >= F) return;
-  const int nc = G * G;
-  const int* __restrict__ cell_start = hdr + VIS_HDR;
-  const int* __restrict__ items = cell_start + nc + 1;
-  const float* __restrict__ wdir = reinterpret_cast<const float*>(items + V);
+  const float* __restrict__ wdir = reinterpret_cast<const float*>(fr.wdir);
   float c[3], P0[3], P1[3], P2[3];
   vis_cam(cam, b, c);
   VisTri t;
@@ -335,10 +311,10 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_tri_kernel(const float* __restr
   if (box.big) return;
   unsigned char* __restrict__ o = vis + (size_t)b * V;
   for (int cy = box.ly; cy <= box.hy; ++cy) {
-    const int s0 = cell_start[cy * G + box.lx], s1 = cell_start[cy * G + box.hx + 1];       // the cells of one row are contiguous
+    const int s0 = fr.cell_start[cy * G + box.lx], s1 = fr.cell_start[cy * G + box.hx + 1];       // the cells of one row are contiguous
     for (int s = s0; s < s1; ++s) {
       const float w[3] = {wdir[3 * (size_t)s], wdir[3 * (size_t)s + 1], wdir[3 * (size_t)s + 2]};
-      if (vis_hit(w, t.nd, t.a, t.q, t.p0, t.tn)) o[items[s]] = 0;
+      if (vis_hit(w, t.nd, t.a, t.q, t.p0, t.tn)) o[fr.items[s]] = 0;
     }
   }
 }
@@ -350,11 +326,10 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_big_kernel(const float* __restr
   __shared__ int list[VIS_BLOCK];
   __shared__ int count;
   const int tid = threadIdx.x, b = blockIdx.y, f = blockIdx.x * VIS_BLOCK + tid;
-  const int* __restrict__ hdr = ws + (size_t)b * wstride;
+  const VisWs<const int*> fr = vis_ws(ws + (size_t)b * wstride, V, G);
+  const int* __restrict__ hdr = fr.hdr;
   if (hdr[0] != 1) return;                                    // uniform
-  const int nc = G * G;
-  const int* __restrict__ items = hdr + VIS_HDR + nc + 1;
-  const float* __restrict__ wdir = reinterpret_cast<const float*>(items + V);
+  const float* __restrict__ wdir = reinterpret_cast<const float*>(fr.wdir);
   const float* __restrict__ vf = verts + (size_t)b * V * 3;
   float c[3], P0[3], P1[3], P2[3];
   vis_cam(cam, b, c);
@@ -374,7 +349,7 @@ __global__ void __launch_bounds__(VIS_BLOCK) vis_big_kernel(const float* __restr
     vis_face(vf, V, faces, list[i], c, P0, P1, P2, t);
     for (int s = tid; s < V; s += VIS_BLOCK) {
       const float w[3] = {wdir[3 * (size_t)s], wdir[3 * (size_t)s + 1], wdir[3 * (size_t)s + 2]};
-      if (vis_hit(w, t.nd, t.a, t.q, t.p0, t.tn)) o[items[s]] = 0;
+      if (vis_hit(w, t.nd, t.a, t.q, t.p0, t.tn)) o[fr.items[s]] = 0;
     }
   }
 }
@@ -388,7 +363,7 @@ int vis_shape(int B, int V, int F, int mode, int grid) {
   return 0;
 }
 
-long long vis_words(int V, int G) { return VIS_HDR + (long long)G * G + 1 + 4ll * V; }
+long long vis_words(int V, int G) { return vis_ws(0ll, V, G).end; }
 
 // what `auto` means: profiles/scan_terms_rate.txt decides
 #define VIS_AUTO_MODE LEMO_VIS_BINNED
