@@ -22,13 +22,12 @@
 #include "ae_engine.hpp"
 #include "conv_common.hpp"
 #include "conv_f16.hpp"
+#include "engine_host.hpp"
 
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
-
-#define CHK_(e) do { int _e = (e); if (_e) return _e; } while (0)
 
 // slots of AeEngine::amax.  0 .. AE_SLOT_DYN - 1 are rewritten every step (zeroed by the optimiser launch and at load)
 #define AE_SLOT_ACT(i) (i)                /* max |output of layer i| (forward) */
@@ -1041,22 +1040,22 @@ static int ae_forward(AeEngine* e, hipStream_t s) {
     const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
     const AeGeo g = geo_plain(H, W);
     // (pooling and zero stuffing keep the maximum: the pooled / stuffed inputs scale by their source's slot)
-    CHK_(AE_CONVS(e, b == 0 ? AE_SLOT_X8 : AE_SLOT_ACT(i0 - 1), 1.f, i0, AE_SLOT_ACT(i0),
+    CHK(AE_CONVS(e, b == 0 ? AE_SLOT_X8 : AE_SLOT_ACT(i0 - 1), 1.f, i0, AE_SLOT_ACT(i0),
                   e->xin[i0], e->theta + e->L[i0].w_off, e->theta + e->n_w + e->L[i0].b_off, nullptr, e->act[i0], g, e->L[i0].cin_pad, e->L[i0].cout_pad, 0, s));
-    CHK_(AE_CONVS(e, AE_SLOT_ACT(i0), 1.f, i2, AE_SLOT_ACT(i2),
+    CHK(AE_CONVS(e, AE_SLOT_ACT(i0), 1.f, i2, AE_SLOT_ACT(i2),
                   e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, 0, s));
-    CHK_(maxpool3s2_fwd(e->act[i2], H, W, e->P[b], e->idx[b], e->L[i2].cout_pad, s, e->nclip, e->cs));
+    CHK(maxpool3s2_fwd(e->act[i2], H, W, e->P[b], e->idx[b], e->L[i2].cout_pad, s, e->nclip, e->cs));
   }
-  CHK_(stuff2_fwd(e->P[4], e->H[5], e->W[5], e->S[0], e->H[4], e->W[4], e->L[10].cin_pad, s, e->nclip, e->cs));
+  CHK(stuff2_fwd(e->P[4], e->H[5], e->W[5], e->S[0], e->H[4], e->W[4], e->L[10].cin_pad, s, e->nclip, e->cs));
   for (int b = 0; b < 5; ++b) {
     const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
     AeGeo g = geo_plain(H, W);
-    CHK_(AE_CONVS(e, AE_SLOT_ACT(i1 - 1), 1.f, i1, AE_SLOT_ACT(i1),
+    CHK(AE_CONVS(e, AE_SLOT_ACT(i1 - 1), 1.f, i1, AE_SLOT_ACT(i1),
                   e->xin[i1], e->theta + e->L[i1].w_off, e->theta + e->n_w + e->L[i1].b_off, nullptr, e->act[i1], g, e->L[i1].cin_pad, e->L[i1].cout_pad, 0, s));
     if (b < 4) {       // straight into the stuffed input of the next block: pixel (y, x) -> (2y, 2x) of the next finer level
       g.out_Wp = e->W[lv - 1] + 2; g.out_HWp = (e->H[lv - 1] + 2) * g.out_Wp; g.out_s = 2;
     }
-    CHK_(AE_CONVS(e, AE_SLOT_ACT(i1), 1.f, i2, AE_SLOT_ACT(i2),
+    CHK(AE_CONVS(e, AE_SLOT_ACT(i1), 1.f, i2, AE_SLOT_ACT(i2),
                   e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, b < 4 ? 0 : 2, s));
   }
   return 0;
@@ -1065,16 +1064,16 @@ static int ae_forward(AeEngine* e, hipStream_t s) {
 static int ae_wgrad_launch(AeEngine* e, hipStream_t s, int mode);
 
 static int ae_train_step(AeEngine* e, hipStream_t s) {
-  CHK_(ae_forward(e, s));
+  CHK(ae_forward(e, s));
   const int H0 = e->H[0], W0 = e->W[0];
   hipLaunchKernelGGL(ae_loss_grad_kernel, dim3((H0 * W0 + 255) / 256, e->nclip), dim3(256), 0, s, (const float*)e->act[19], (const float*)e->x8,
                      (const float*)e->moc, e->dp[19], H0, W0, e->ctr, lr_decimal(e->lr), e->cs);
-  CHK_((int)hipGetLastError());
+  CHK((int)hipGetLastError());
   // ---- decoder, last block first
   for (int b = 4; b >= 0; --b) {
     const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
     const AeGeo g = geo_plain(H, W);
-    CHK_(AE_CONVS(e, i2 == 19 ? AE_SLOT_LOSS : AE_SLOT_DP(i2), 1.f, i2, AE_SLOT_DP(i1),
+    CHK(AE_CONVS(e, i2 == 19 ? AE_SLOT_LOSS : AE_SLOT_DP(i2), 1.f, i2, AE_SLOT_DP(i1),
                   e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i1], e->dp[i1], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));     // * lrelu'(act[i1])
     // adjoint of (stuffing, transposed conv): only the even pixels of d(stuffed input) exist downstream -> enumerate the
     // coarse grid, centre taps at (2i, 2j); times lrelu' of the previous block's output (read where it lives: stuffed in S[b])
@@ -1083,24 +1082,24 @@ static int ae_train_step(AeEngine* e, hipStream_t s) {
     gs.in_Wp = W + 2; gs.in_HWp = (H + 2) * (W + 2); gs.in_s = 2;
     gs.aux_Wp = gs.in_Wp; gs.aux_HWp = gs.in_HWp; gs.aux_s = 2;
     float* dst = b > 0 ? e->dp[i1 - 1] : e->dP[4];
-    if (b > 0) CHK_(AE_CONVS(e, AE_SLOT_DP(i1), 1.f, i1, AE_SLOT_DP(i1 - 1),
+    if (b > 0) CHK(AE_CONVS(e, AE_SLOT_DP(i1), 1.f, i1, AE_SLOT_DP(i1 - 1),
                              e->dp[i1], e->wb + e->L[i1].wb_off, nullptr, e->S[b], dst, gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 1, s));
-    else       CHK_(AE_CONVS(e, AE_SLOT_DP(i1), 1.f, i1, AE_SLOT_DPOOL(4),
+    else       CHK(AE_CONVS(e, AE_SLOT_DP(i1), 1.f, i1, AE_SLOT_DPOOL(4),
                              e->dp[i1], e->wb + e->L[i1].wb_off, e->zero_bias, nullptr, dst, gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 2, s));   // the latent has no activation
   }
   // ---- encoder, last block first
   for (int b = 4; b >= 0; --b) {
     const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
     const AeGeo g = geo_plain(H, W);
-    CHK_(maxpool3s2_bwd(e->dP[b], e->idx[b], e->act[i2], e->dp[i2], H, W, e->L[i2].cout_pad, s, e->nclip, e->cs));
+    CHK(maxpool3s2_bwd(e->dP[b], e->idx[b], e->act[i2], e->dp[i2], H, W, e->L[i2].cout_pad, s, e->nclip, e->cs));
     // (the max-pool adjoint adds at most four window gradients into one pixel, times lrelu' <= 1: dp[i2] is bounded by 4 x the pooled gradient's maximum)
-    CHK_(AE_CONVS(e, AE_SLOT_DPOOL(b), 4.f, i2, AE_SLOT_DP(i0),
+    CHK(AE_CONVS(e, AE_SLOT_DPOOL(b), 4.f, i2, AE_SLOT_DP(i0),
                   e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i0], e->dp[i0], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
-    if (b > 0) CHK_(AE_CONVS(e, AE_SLOT_DP(i0), 1.f, i0, AE_SLOT_DPOOL(b - 1),
+    if (b > 0) CHK(AE_CONVS(e, AE_SLOT_DP(i0), 1.f, i0, AE_SLOT_DPOOL(b - 1),
                              e->dp[i0], e->wb + e->L[i0].wb_off, e->zero_bias, nullptr, e->dP[b - 1], g, e->L[i0].cout_pad, e->L[i0].cin_pad, 2, s));
   }
   // ---- all weight and bias gradients
-  CHK_(ae_wgrad_launch(e, s, 0));
+  CHK(ae_wgrad_launch(e, s, 0));
   // ---- Adam
   AeAdamArgs A;
   for (int i = 0; i < AE_NLAYER; ++i) {
@@ -1148,17 +1147,11 @@ static AePackArgs ae_pack_args(const AeEngine* e) {
 }
 
 static int ae_capture(AeEngine* e, hipStream_t s, int steps, hipGraphExec_t* out) {
-  hipGraph_t g = nullptr;
-  int rc = (int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-  if (rc) return rc;
-  for (int i = 0; i < steps && !rc; ++i) rc = ae_train_step(e, s);
-  const int ec = (int)hipStreamEndCapture(s, &g);
-  if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-  if (ec) return ec;
-  const int ic = (int)hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (!ic) (void)hipGraphUpload(*out, s);
-  return ic;
+  return capture_graph(out, s, true, [&] {
+    int rc = 0;
+    for (int i = 0; i < steps && !rc; ++i) rc = ae_train_step(e, s);
+    return rc;
+  });
 }
 
 }  // namespace lemo
@@ -1200,7 +1193,7 @@ void* lemo_ae_create(const lemo_ae_desc* d) {
 void lemo_ae_destroy(void* h) {
   AeEngine* e = (AeEngine*)h;
   if (!e) return;
-  for (int l = 0; l < 2; ++l) if (e->exec[l]) (void)hipGraphExecDestroy(e->exec[l]);
+  destroy_graphs(e->exec, 2);
   delete e;
 }
 

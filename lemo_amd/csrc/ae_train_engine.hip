@@ -20,7 +20,6 @@
 #include <cstring>
 #include <new>
 
-#define CHK_(e) do { int _e = (e); if (_e) return _e; } while (0)
 #define AET_GROUPS 8              // image groups of the weight-gradient reduction (at most; fewer when bs < 8)
 #define AET_MAX_BS 128
 #define AET_LOSS_BLOCK 256
@@ -346,17 +345,17 @@ static int aet_forward(AetEngine* e, hipStream_t s) {
   for (int b = 0; b < 5; ++b) {
     const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
     const AeGeo g = geo_plain(H, W);
-    CHK_(AET_CONV(e, e->xin[i0], e->theta + e->L[i0].w_off, e->theta + e->n_w + e->L[i0].b_off, nullptr, e->act[i0], g, e->L[i0].cin_pad, e->L[i0].cout_pad, 0, s));
-    CHK_(AET_CONV(e, e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, 0, s));
-    CHK_(maxpool3s2_fwd(e->act[i2], H, W, e->P[b], e->idx[b], e->L[i2].cout_pad, s, e->bs, e->cs));
+    CHK(AET_CONV(e, e->xin[i0], e->theta + e->L[i0].w_off, e->theta + e->n_w + e->L[i0].b_off, nullptr, e->act[i0], g, e->L[i0].cin_pad, e->L[i0].cout_pad, 0, s));
+    CHK(AET_CONV(e, e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, 0, s));
+    CHK(maxpool3s2_fwd(e->act[i2], H, W, e->P[b], e->idx[b], e->L[i2].cout_pad, s, e->bs, e->cs));
   }
-  CHK_(stuff2_fwd(e->P[4], e->H[5], e->W[5], e->S[0], e->H[4], e->W[4], e->L[10].cin_pad, s, e->bs, e->cs));
+  CHK(stuff2_fwd(e->P[4], e->H[5], e->W[5], e->S[0], e->H[4], e->W[4], e->L[10].cin_pad, s, e->bs, e->cs));
   for (int b = 0; b < 5; ++b) {
     const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
     AeGeo g = geo_plain(H, W);
-    CHK_(AET_CONV(e, e->xin[i1], e->theta + e->L[i1].w_off, e->theta + e->n_w + e->L[i1].b_off, nullptr, e->act[i1], g, e->L[i1].cin_pad, e->L[i1].cout_pad, 0, s));
+    CHK(AET_CONV(e, e->xin[i1], e->theta + e->L[i1].w_off, e->theta + e->n_w + e->L[i1].b_off, nullptr, e->act[i1], g, e->L[i1].cin_pad, e->L[i1].cout_pad, 0, s));
     if (b < 4) { g.out_Wp = e->W[lv - 1] + 2; g.out_HWp = (e->H[lv - 1] + 2) * g.out_Wp; g.out_s = 2; }     // into the next block's stuffed input
-    CHK_(AET_CONV(e, e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, b < 4 ? 0 : 2, s));
+    CHK(AET_CONV(e, e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, b < 4 ? 0 : 2, s));
   }
   return 0;
 }
@@ -367,7 +366,7 @@ static int aet_loss(AetEngine* e, bool step, hipStream_t s) {
   AetLossArgs A{e->act[19], e->ybuf, e->dp[19], e->lpart, e->ctr, H, W, e->cs, e->lr, step ? 1 : 0,
                 (float)(e->w_body / n1), (float)(e->w_v / n2), (float)(e->w_c / n3)};
   hipLaunchKernelGGL(aet_loss_kernel, dim3(e->nblk / e->bs, e->bs), dim3(AET_LOSS_BLOCK), 0, s, A);
-  CHK_((int)hipGetLastError());
+  CHK((int)hipGetLastError());
   hipLaunchKernelGGL(aet_loss_reduce_kernel, dim3(1), dim3(256), 0, s, (const float*)e->lpart, e->nblk, (float)(1.0 / n1), (float)(1.0 / n2),
                      (float)(1.0 / n3), e->w_body, e->w_v, e->w_c, e->losses);
   return (int)hipGetLastError();
@@ -416,30 +415,30 @@ static int aet_wgrad(AetEngine* e, hipStream_t s) {
 }
 
 static int aet_train_step(AetEngine* e, hipStream_t s) {
-  CHK_(aet_forward(e, s));
-  CHK_(aet_loss(e, true, s));
+  CHK(aet_forward(e, s));
+  CHK(aet_loss(e, true, s));
   // ---- decoder, last block first
   for (int b = 4; b >= 0; --b) {
     const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
     const AeGeo g = geo_plain(H, W);
-    CHK_(AET_CONV(e, e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i1], e->dp[i1], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
+    CHK(AET_CONV(e, e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i1], e->dp[i1], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
     // adjoint of (stuffing, transposed conv): the coarse grid, centre taps at (2i, 2j), times lrelu' of the previous block's output
     const int h = e->H[lv + 1], w = e->W[lv + 1];
     AeGeo gs = geo_plain(h, w);
     gs.in_Wp = W + 2; gs.in_HWp = (H + 2) * (W + 2); gs.in_s = 2;
     gs.aux_Wp = gs.in_Wp; gs.aux_HWp = gs.in_HWp; gs.aux_s = 2;
-    if (b > 0) CHK_(AET_CONV(e, e->dp[i1], e->wb + e->L[i1].wb_off, nullptr, e->S[b], e->dp[i1 - 1], gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 1, s));
-    else       CHK_(AET_CONV(e, e->dp[i1], e->wb + e->L[i1].wb_off, e->zero_bias, nullptr, e->dP[4], gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 2, s));
+    if (b > 0) CHK(AET_CONV(e, e->dp[i1], e->wb + e->L[i1].wb_off, nullptr, e->S[b], e->dp[i1 - 1], gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 1, s));
+    else       CHK(AET_CONV(e, e->dp[i1], e->wb + e->L[i1].wb_off, e->zero_bias, nullptr, e->dP[4], gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 2, s));
   }
   // ---- encoder, last block first
   for (int b = 4; b >= 0; --b) {
     const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
     const AeGeo g = geo_plain(H, W);
-    CHK_(maxpool3s2_bwd(e->dP[b], e->idx[b], e->act[i2], e->dp[i2], H, W, e->L[i2].cout_pad, s, e->bs, e->cs));
-    CHK_(AET_CONV(e, e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i0], e->dp[i0], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
-    if (b > 0) CHK_(AET_CONV(e, e->dp[i0], e->wb + e->L[i0].wb_off, e->zero_bias, nullptr, e->dP[b - 1], g, e->L[i0].cout_pad, e->L[i0].cin_pad, 2, s));
+    CHK(maxpool3s2_bwd(e->dP[b], e->idx[b], e->act[i2], e->dp[i2], H, W, e->L[i2].cout_pad, s, e->bs, e->cs));
+    CHK(AET_CONV(e, e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i0], e->dp[i0], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
+    if (b > 0) CHK(AET_CONV(e, e->dp[i0], e->wb + e->L[i0].wb_off, e->zero_bias, nullptr, e->dP[b - 1], g, e->L[i0].cout_pad, e->L[i0].cin_pad, 2, s));
   }
-  CHK_(aet_wgrad(e, s));
+  CHK(aet_wgrad(e, s));
   return ae_adam_launch(aet_adam_args(e), 1, s);
 }
 
@@ -468,12 +467,12 @@ static int aet_epoch_block(const AetEngine* e, const lemo_aetrain_epoch_desc* d,
 
 // one step of an epoch: every kernel reads the step from the device-side cursor
 static int aet_epoch_step(AetEngine* e, bool train, hipStream_t s) {
-  CHK_(aet_assemble(EpochBlock{}, aet_block(e), 0, e->x8, e->cs, e->ybuf, e->bs, e->H[0], e->W[0], s));
+  CHK(aet_assemble(EpochBlock{}, aet_block(e), 0, e->x8, e->cs, e->ybuf, e->bs, e->H[0], e->W[0], s));
   if (train) {
-    CHK_(aet_train_step(e, s));
+    CHK(aet_train_step(e, s));
   } else {
-    CHK_(aet_forward(e, s));
-    CHK_(aet_loss(e, false, s));
+    CHK(aet_forward(e, s));
+    CHK(aet_loss(e, false, s));
   }
   return ep_end(aet_block(e), e->losses, 4, s);
 }
@@ -509,8 +508,8 @@ void* lemo_aetrain_create(const lemo_aetrain_desc* d) {
 void lemo_aetrain_destroy(void* h) {
   AetEngine* e = (AetEngine*)h;
   if (!e) return;
-  if (e->exec) (void)hipGraphExecDestroy(e->exec);
-  for (int k = 0; k < 2; ++k) if (e->exec_ep[k]) (void)hipGraphExecDestroy(e->exec_ep[k]);
+  destroy_graphs(&e->exec, 1);
+  destroy_graphs(e->exec_ep, 2);
   delete e;
 }
 
@@ -519,10 +518,10 @@ int lemo_aetrain_load(void* h, const float* flat, void* stream) {
   if (!e || !flat) return LEMO_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const size_t n_all = (size_t)e->n_w + e->n_b;
-  CHK_(ae_pack_launch(aet_pack_args(e), false, flat, e->theta, e->wb, s));
-  CHK_((int)hipMemsetAsync(e->m, 0, sizeof(float) * n_all, s));          // a fresh optimizer
-  CHK_((int)hipMemsetAsync(e->v, 0, sizeof(float) * n_all, s));
-  CHK_((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
+  CHK(ae_pack_launch(aet_pack_args(e), false, flat, e->theta, e->wb, s));
+  CHK((int)hipMemsetAsync(e->m, 0, sizeof(float) * n_all, s));          // a fresh optimizer
+  CHK((int)hipMemsetAsync(e->v, 0, sizeof(float) * n_all, s));
+  CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
   e->loaded = 1;
   return 0;
 }
@@ -532,26 +531,16 @@ int lemo_aetrain_step(void* h, const float* x, const float* y, int n, float* los
   if (!e || !x || !y || n < 1) return LEMO_ERR_ARG;
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
-  CHK_(aet_stage(e, x, y, s));
+  CHK(aet_stage(e, x, y, s));
   for (int i = 0; i < n; ++i) {
     if (e->use_graph) {
-      if (!e->exec) {
-        hipGraph_t g = nullptr;
-        CHK_((int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = aet_train_step(e, s);
-        const int ec = (int)hipStreamEndCapture(s, &g);
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (ec) return ec;
-        const int ic = (int)hipGraphInstantiate(&e->exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ic) { e->exec = nullptr; return ic; }
-      }
-      CHK_((int)hipGraphLaunch(e->exec, s));
+      if (!e->exec) CHK(capture_graph(&e->exec, s, false, [&] { return aet_train_step(e, s); }));
+      CHK((int)hipGraphLaunch(e->exec, s));
     } else {
-      CHK_(aet_train_step(e, s));
+      CHK(aet_train_step(e, s));
     }
   }
-  if (losses) CHK_((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 4, hipMemcpyDeviceToDevice, s));
+  if (losses) CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
@@ -560,14 +549,14 @@ int lemo_aetrain_eval(void* h, const float* x, const float* y, float* losses, fl
   if (!e || !x || !y || !losses) return LEMO_ERR_ARG;
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
-  CHK_(aet_stage(e, x, y, s));
-  CHK_(aet_forward(e, s));
-  CHK_(aet_loss(e, false, s));
-  CHK_((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 4, hipMemcpyDeviceToDevice, s));
+  CHK(aet_stage(e, x, y, s));
+  CHK(aet_forward(e, s));
+  CHK(aet_loss(e, false, s));
+  CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 4, hipMemcpyDeviceToDevice, s));
   if (rec) {
     hipLaunchKernelGGL(aet_rec_kernel, dim3((e->H[0] * e->W[0] + 255) / 256, e->bs), dim3(256), 0, s, (const float*)e->act[19], rec,
                        e->H[0], e->W[0], e->cs);
-    CHK_((int)hipGetLastError());
+    CHK((int)hipGetLastError());
   }
   return 0;
 }
@@ -586,7 +575,7 @@ int lemo_aetrain_grads(void* h, float* flat_out, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const AeAdamArgs A = aet_adam_args(e);
   hipLaunchKernelGGL(aet_grad_kernel, dim3((A.n_all + 255) / 256), dim3(256), 0, s, A, e->gpk);
-  CHK_((int)hipGetLastError());
+  CHK((int)hipGetLastError());
   return ae_pack_launch(aet_pack_args(e), true, e->gpk, flat_out, nullptr, s);
 }
 
@@ -594,15 +583,15 @@ int lemo_aetrain_epoch(void* h, const lemo_aetrain_epoch_desc* d, void* stream) 
   AetEngine* e = (AetEngine*)h;
   if (!e || !d || !d->log) return LEMO_ERR_ARG;
   EpochBlock B;
-  CHK_(aet_epoch_block(e, d, &B));
+  CHK(aet_epoch_block(e, d, &B));
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const bool train = d->train != 0;
-  CHK_(ep_begin(B, aet_block(e), s));
-  if (e->use_graph) CHK_(capture_chain(&e->exec_ep[train], s, [&] { return aet_epoch_step(e, train, s); }));
+  CHK(ep_begin(B, aet_block(e), s));
+  if (e->use_graph && !e->exec_ep[train]) CHK(capture_graph(&e->exec_ep[train], s, false, [&] { return aet_epoch_step(e, train, s); }));
   for (int i = 0; i < d->n_steps; ++i) {
-    if (e->use_graph) CHK_((int)hipGraphLaunch(e->exec_ep[train], s));
-    else CHK_(aet_epoch_step(e, train, s));
+    if (e->use_graph) CHK((int)hipGraphLaunch(e->exec_ep[train], s));
+    else CHK(aet_epoch_step(e, train, s));
   }
   return 0;
 }
@@ -611,7 +600,7 @@ int lemo_aetrain_batch(void* h, const lemo_aetrain_epoch_desc* d, int step, floa
   AetEngine* e = (AetEngine*)h;
   if (!e || !x || !y) return LEMO_ERR_ARG;
   EpochBlock B;
-  CHK_(aet_epoch_block(e, d, &B));
+  CHK(aet_epoch_block(e, d, &B));
   if (step < 0 || step >= d->n_steps) return LEMO_ERR_ARG;
   return aet_assemble_api(B, step, x, y, e->bs, e->H[0], e->W[0], (hipStream_t)stream);
 }
@@ -629,9 +618,9 @@ int lemo_aetrain_state_save(void* h, float* out, void* stream) {
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const AePackArgs P = aet_pack_args(e);
-  CHK_(ae_pack_launch(P, true, e->theta, out, nullptr, s));
-  CHK_(ae_pack_launch(P, true, e->m, out + e->n_flat, nullptr, s));
-  CHK_(ae_pack_launch(P, true, e->v, out + 2 * (size_t)e->n_flat, nullptr, s));
+  CHK(ae_pack_launch(P, true, e->theta, out, nullptr, s));
+  CHK(ae_pack_launch(P, true, e->m, out + e->n_flat, nullptr, s));
+  CHK(ae_pack_launch(P, true, e->v, out + 2 * (size_t)e->n_flat, nullptr, s));
   return train_step_counter(e->ctr, out + 3 * (size_t)e->n_flat, true, s);
 }
 
@@ -642,11 +631,11 @@ int lemo_aetrain_state_load(void* h, const float* in, void* stream) {
   const AePackArgs P = aet_pack_args(e);
   // the moments take the parameters' packing; the backward pack it writes on the way goes to the gradient scratch (gpk holds
   // n_w + n_b >= n_wb floats and is rewritten by every lemo_aetrain_grads), then the parameters' own backward pack to wb
-  CHK_(ae_pack_launch(P, false, in + e->n_flat, e->m, e->gpk, s));
-  CHK_(ae_pack_launch(P, false, in + 2 * (size_t)e->n_flat, e->v, e->gpk, s));
-  CHK_(ae_pack_launch(P, false, in, e->theta, e->wb, s));
-  CHK_((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
-  CHK_(train_step_counter(e->ctr, const_cast<float*>(in) + 3 * (size_t)e->n_flat, false, s));
+  CHK(ae_pack_launch(P, false, in + e->n_flat, e->m, e->gpk, s));
+  CHK(ae_pack_launch(P, false, in + 2 * (size_t)e->n_flat, e->v, e->gpk, s));
+  CHK(ae_pack_launch(P, false, in, e->theta, e->wb, s));
+  CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
+  CHK(train_step_counter(e->ctr, const_cast<float*>(in) + 3 * (size_t)e->n_flat, false, s));
   e->loaded = 1;
   return 0;
 }
@@ -657,7 +646,7 @@ int lemo_aetrain_pool_winners(void* h, int block, unsigned char* out, void* stre
   if (!e->loaded) return LEMO_ERR_STATE;
   const size_t n = (size_t)e->L[2 * block + 1].cout_pad * e->H[block + 1] * e->W[block + 1];
   for (int c = 0; c < e->bs; ++c)                                  // (idx is carved in floats: image c's bytes are 4 c cs further)
-    CHK_((int)hipMemcpyAsync(out + c * n, e->idx[block] + 4 * (size_t)c * e->cs, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    CHK((int)hipMemcpyAsync(out + c * n, e->idx[block] + 4 * (size_t)c * e->cs, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }
 

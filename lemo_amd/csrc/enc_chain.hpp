@@ -2,10 +2,9 @@
 // launch sequences shared by the two engines (lemo_fit_desc / lemo_prox_desc carry the same enc_* fields).
 #pragma once
 #include "kernels.hpp"
+#include "engine_host.hpp"
 
 namespace lemo {
-
-#define ENC_CHK(e) do { int _e = (e); if (_e) return _e; } while (0)
 
 // conv variant 7 = variant 5 + the fused head / tail (conv_head_kernels.hip): layers 0 and 1 ride with the marker image / the image gradient
 template <class D> static inline bool enc_fused_head(const D& d) {
@@ -46,7 +45,7 @@ static inline int enc_layer(const D& d, int l, bool bwd, const float* src, float
   if (d.conv_variant >= 3 && w3 && conv3x3_split_supported(H, W, cin, cout))
     return conv3x3_mfma_split(src, w3, wt, bias, aux, dst, H, W, cin, cout, epi, s, nullptr, d.conv_variant >= 4 ? 2 : 3,
                               bwd ? d.enc_wbwd3_inv[l] : d.enc_w3_inv[l]);
-  if (d.conv_variant >= 2 && 127 + 2 * (127 / W + 1) + 2 * (W + 2) + 3 <= 416)
+  if (d.conv_variant >= 2 && 127 + 2 * (127 / W + 1) + 2 * (W + 2) + 3 <= 416)      // priors.py: lds_tile_fits(W)
     return conv3x3_mfma_lds(src, wt, wt2, bias, aux, dst, H, W, cin, cout, epi, s);
   return conv3x3_mfma(src, wt, bias, aux, dst, H, W, cin, cout, epi, d.conv_variant >= 2 ? 1 : d.conv_variant, s);
 }
@@ -61,12 +60,12 @@ static inline int enc_chain_fwd(const D& d, int H, int W, hipStream_t s, int l_f
   while (l < l_end) {
     if (d.conv_variant >= 5 && d.conv_variant != 10 && l + 1 < l_end && d.enc_w3[l] && d.enc_w3[l + 1] &&
         conv3x3_pair_supported(H, W, d.enc_ch[l], d.enc_ch[l + 1], d.enc_ch[l + 2])) {
-      ENC_CHK(conv3x3_pair_f16(d.act[l], d.enc_w3[l], d.enc_w3_inv[l], d.enc_b[l], nullptr, d.act[l + 1],
+      CHK(conv3x3_pair_f16(d.act[l], d.enc_w3[l], d.enc_w3_inv[l], d.enc_b[l], nullptr, d.act[l + 1],
                                                                            d.enc_w3[l + 1], d.enc_w3_inv[l + 1], d.enc_b[l + 1], nullptr, d.act[l + 2],
                                                                            H, W, 0, s, nullptr));
       l += 2;
     } else {
-      ENC_CHK(enc_layer(d, l, false, d.act[l], d.act[l + 1], H, W, s));
+      CHK(enc_layer(d, l, false, d.act[l], d.act[l + 1], H, W, s));
       ++l;
     }
   }
@@ -82,18 +81,33 @@ static inline int enc_chain_bwd(const D& d, int H, int W, hipStream_t s, int* cu
   while (l >= l_last) {
     if (d.conv_variant >= 5 && d.conv_variant != 10 && l - 1 >= l_last && d.enc_wbwd3[l] && d.enc_wbwd3[l - 1] &&
         conv3x3_pair_supported(H, W, d.enc_ch[l + 1], d.enc_ch[l], d.enc_ch[l - 1])) {
-      ENC_CHK(conv3x3_pair_f16(d.dact[cur], d.enc_wbwd3[l], d.enc_wbwd3_inv[l], nullptr, d.act[l], nullptr,
+      CHK(conv3x3_pair_f16(d.dact[cur], d.enc_wbwd3[l], d.enc_wbwd3_inv[l], nullptr, d.act[l], nullptr,
                                                                            d.enc_wbwd3[l - 1], d.enc_wbwd3_inv[l - 1], nullptr, d.act[l - 1],
                                                                            d.dact[1 - cur], H, W, 1, s, nullptr));
       l -= 2;
     } else {
-      ENC_CHK(enc_layer(d, l, true, d.dact[cur], d.dact[1 - cur], H, W, s));
+      CHK(enc_layer(d, l, true, d.dact[cur], d.dact[1 - cur], H, W, s));
       --l;
     }
     cur = 1 - cur;
   }
   *cur_out = cur;
   return 0;
+}
+
+// the encoder's forward head: marker image + layer 0 (with layers 1 and 2 where the variant fuses them) as one launch, then the chain up
+// to l_end.  nrows: rows per frame of d.verts
+template <class D> static inline int enc_head_fwd(const D& d, int nrows, int H, int W, hipStream_t s, int l_end) {
+  const int B = d.B, nj = d.body.nj;
+  if (enc_fused_head3(d))
+    CHK(enc_head3(d.fit, d.verts, nrows, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.enc_w3[1], d.enc_w3_inv[1], d.enc_b[1], d.enc_w3[2],
+                  d.enc_w3_inv[2], d.enc_b[2], d.x0, d.canon, d.act[1], d.act[2], d.act[3], s));
+  else if (enc_fused_head(d))
+    CHK(enc_head(d.fit, d.verts, nrows, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.enc_w3[1], d.enc_w3_inv[1], d.enc_b[1], d.x0, d.canon,
+                 d.act[1], d.act[2], s));
+  else
+    CHK(marker_c1(d.fit, d.verts, nrows, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.x0, d.canon, d.act[1], d.enc_ch[1], s));
+  return enc_chain_fwd(d, H, W, s, enc_fused_head3(d) ? 3 : (enc_fused_head(d) ? 2 : 1), l_end);
 }
 
 // conv variant 9's step schedule (lemo_fit_step; LEMO_ENC_TURN=0 keeps the chain above): layer 9 forward, the smoothness loss gradient

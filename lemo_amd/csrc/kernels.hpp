@@ -267,6 +267,23 @@ struct StateCopy {
   int* nonfinite;                  // [2] zeroed when non-null (load)
 };
 int state_copy(const StateCopy& a, hipStream_t s);
+// the njobs tensors of an engine (eng[i], B * width[i] floats) and its step counter <-> the caller's (usr[i], step_usr); load: usr -> eng
+static inline int state_io(float* const* eng, float* const* usr, const int* width, int njobs, int B, int* step_eng, int* step_usr,
+                           int* nonfinite, bool load, hipStream_t s) {
+  if (njobs > STATE_MAX_JOBS) return LEMO_ERR_ARG;
+  StateCopy a{};
+  for (int i = 0; i < njobs; ++i) {
+    if (!eng[i] || !usr[i]) return LEMO_ERR_ARG;
+    a.src[i] = load ? usr[i] : eng[i];
+    a.dst[i] = load ? eng[i] : usr[i];
+    a.n[i] = B * width[i];
+  }
+  a.njobs = njobs;
+  a.step_src = load ? step_usr : step_eng;
+  a.step_dst = load ? step_eng : step_usr;
+  a.nonfinite = load ? nonfinite : nullptr;
+  return state_copy(a, s);
+}
 
 // ---------------- marker_kernels.hip ----------------
 int reconstruct_global_body(const float* in, int T, int J, double rot0, float* out, hipStream_t s, const double* rot0_dev = nullptr);

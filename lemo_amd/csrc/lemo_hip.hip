@@ -8,9 +8,6 @@
 
 using namespace lemo;
 
-#define S(x) ((hipStream_t)(x))
-#define CHK(e) do { int _e = (e); if (_e) return _e; } while (0)
-
 namespace lemo {
 
 // the only place that sets MaxDynamicSharedMemorySize (kernels.hpp)
@@ -315,17 +312,11 @@ struct FitEngine {
 static int fit_iteration(const lemo_fit_desc& d, hipStream_t s, bool first, bool last, FitSide* fs, bool turn);
 
 static int capture_iterations(FitEngine* e, hipStream_t s, int iters, hipGraphExec_t* out) {
-  hipGraph_t g = nullptr;
-  CHK((int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (int i = 0; i < iters && !rc; ++i) rc = fit_iteration(e->d, s, i == 0, i == iters - 1, &e->fs, e->turn);
-  const int ec = (int)hipStreamEndCapture(s, &g);
-  if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-  CHK(ec);
-  const int ic = (int)hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (!ic) (void)hipGraphUpload(*out, s);       // the first replay then does not pay for the upload (lemo_fit_prepare)
-  return ic;
+  return capture_graph(out, s, true, [&] {
+    int rc = 0;
+    for (int i = 0; i < iters && !rc; ++i) rc = fit_iteration(e->d, s, i == 0, i == iters - 1, &e->fs, e->turn);
+    return rc;
+  });
 }
 
 // n iterations as replays; launch = false only captures what is missing.
@@ -442,15 +433,7 @@ static int fit_forward(const lemo_fit_desc& d, hipStream_t s, bool finalize, boo
   }
   // marker image + first encoder layer in one launch (x0 is still written: parity tests read it)
   if (stages & 4u) {
-  if (enc_fused_head3(d))
-    CHK(enc_head3(d.fit, d.verts, d.nrows, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.enc_w3[1], d.enc_w3_inv[1], d.enc_b[1], d.enc_w3[2],
-                  d.enc_w3_inv[2], d.enc_b[2], d.x0, d.canon, d.act[1], d.act[2], d.act[3], s));
-  else if (enc_fused_head(d))
-    CHK(enc_head(d.fit, d.verts, d.nrows, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.enc_w3[1], d.enc_w3_inv[1], d.enc_b[1], d.x0, d.canon,
-                 d.act[1], d.act[2], s));
-  else
-    CHK(marker_c1(d.fit, d.verts, d.nrows, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.x0, d.canon, d.act[1], d.enc_ch[1], s));
-  CHK(enc_chain_fwd(d, H, W, s, enc_fused_head3(d) ? 3 : (enc_fused_head(d) ? 2 : 1), tn ? 9 : 10));
+  CHK(enc_head_fwd(d, d.nrows, H, W, s, tn ? 9 : 10));
   }
   const double cnt = (double)d.enc_ch[10] * H * (W - 1);
   const float coef2 = (float)((double)d.weights_host[5] * 2.0 / cnt);
@@ -558,7 +541,7 @@ void* lemo_fit_create(const lemo_fit_desc* d) {
 void lemo_fit_destroy(void* h) {
   FitEngine* e = (FitEngine*)h;
   if (!e) return;
-  for (int l = 0; l <= FIT_MAXG; ++l) if (e->exec[l]) (void)hipGraphExecDestroy(e->exec[l]);
+  destroy_graphs(e->exec, FIT_MAXG + 1);
   if (e->fs.fork) (void)hipEventDestroy(e->fs.fork);
   if (e->fs.join) (void)hipEventDestroy(e->fs.join);
   if (e->fs.side) { (void)hipStreamSynchronize(e->fs.side); (void)hipStreamDestroy(e->fs.side); }
@@ -611,17 +594,15 @@ int lemo_fit_census(void* h, int reps, float* ms_out, void* stream) {
   int rc = 0;
   for (int k = 0; k <= LEMO_FIT_NSTAGE && !rc; ++k) {           // k == LEMO_FIT_NSTAGE: the whole forward + backward (no update)
     const unsigned mask = k == LEMO_FIT_NSTAGE ? ~0u : (1u << k);
-    hipGraph_t g = nullptr;
     hipGraphExec_t x = nullptr;
-    rc = (int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-    for (int r = 0; r < reps && !rc; ++r) {
-      if (mask & 15u) rc = fit_forward(d, s, false, true, mask, nullptr, e->turn);
-      if (!rc && (mask & 112u)) rc = fit_backward(d, s, false, false, mask, nullptr, e->turn);
-    }
-    const int ec = (int)hipStreamEndCapture(s, &g);
-    if (!rc) rc = ec;
-    if (!rc) rc = (int)hipGraphInstantiate(&x, g, nullptr, nullptr, 0);
-    if (g) (void)hipGraphDestroy(g);
+    rc = capture_graph(&x, s, false, [&] {
+      int brc = 0;
+      for (int r = 0; r < reps && !brc; ++r) {
+        if (mask & 15u) brc = fit_forward(d, s, false, true, mask, nullptr, e->turn);
+        if (!brc && (mask & 112u)) brc = fit_backward(d, s, false, false, mask, nullptr, e->turn);
+      }
+      return brc;
+    });
     if (!rc) {
       rc = (int)hipGraphLaunch(x, s);                              // once untimed (upload, caches), once timed
       if (!rc) rc = (int)hipEventRecord(e0, s);
@@ -632,7 +613,7 @@ int lemo_fit_census(void* h, int reps, float* ms_out, void* stream) {
       if (!rc) rc = (int)hipEventElapsedTime(&ms, e0, e1);
       ms_out[k] = ms / (float)reps;
     }
-    if (x) (void)hipGraphExecDestroy(x);
+    destroy_graphs(&x, 1);
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
@@ -646,21 +627,10 @@ static int fit_state_io(FitEngine* e, const lemo_fit_state* st, bool load, hipSt
   if (!e || !st || !st->transl || !st->rot6d || !st->other || !st->step) return LEMO_ERR_ARG;
   const lemo_fit_desc& d = e->d;
   if (!d.rot6d || !d.other || !d.step_ctr) return LEMO_ERR_STATE;
-  StateCopy a{};
   float* eng[9] = {d.transl, d.rot6d, d.other, d.adam_m[0], d.adam_m[1], d.adam_m[2], d.adam_v[0], d.adam_v[1], d.adam_v[2]};
   float* usr[9] = {st->transl, st->rot6d, st->other, st->adam_m[0], st->adam_m[1], st->adam_m[2], st->adam_v[0], st->adam_v[1], st->adam_v[2]};
-  const int width[3] = {3, 6, 56};
-  for (int i = 0; i < 9; ++i) {
-    if (!eng[i] || !usr[i]) return LEMO_ERR_ARG;
-    a.src[i] = load ? usr[i] : eng[i];
-    a.dst[i] = load ? eng[i] : usr[i];
-    a.n[i] = d.B * width[i % 3];
-  }
-  a.njobs = 9;
-  a.step_src = load ? st->step : d.step_ctr;
-  a.step_dst = load ? d.step_ctr : st->step;
-  a.nonfinite = load ? d.nonfinite : nullptr;
-  return state_copy(a, s);
+  const int width[9] = {3, 6, 56, 3, 6, 56, 3, 6, 56};
+  return state_io(eng, usr, width, 9, d.B, d.step_ctr, st->step, d.nonfinite, load, s);
 }
 int lemo_fit_load_state(void* h, const lemo_fit_state* st, void* stream) { return fit_state_io((FitEngine*)h, st, true, S(stream)); }
 int lemo_fit_save_state(void* h, const lemo_fit_state* st, void* stream) { return fit_state_io((FitEngine*)h, st, false, S(stream)); }

@@ -13,9 +13,6 @@ int prox_tail(const lemo_prox_desc& d, bool update, hipStream_t s);
 }
 using namespace lemo;
 
-#define CHK(x) do { int e_ = (x); if (e_) return e_; } while (0)
-static inline hipStream_t S(void* s) { return (hipStream_t)s; }
-
 static const int PROX_LEVELS = 2;
 static const int PROX_UNROLL[PROX_LEVELS] = {10, 1};
 
@@ -44,15 +41,7 @@ static int prox_closure(const lemo_prox_desc& d, hipStream_t s, bool fused_tail 
   CHK(lbs_verts_fwd(d.skin, d.pose.Xg, d.Bp, d.pose.A, nj, d.transl, nullptr, d.V, B, d.verts, d.v_posed, s, nullptr, d.pose.XgS));
   // ---- loss: per-frame terms, dense SDF term, smoothness prior through the encoder
   CHK(prox_frame_dense(d, s));
-  if (enc_fused_head3(d))
-    CHK(enc_head3(d.fit, d.verts, d.V, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.enc_w3[1], d.enc_w3_inv[1], d.enc_b[1], d.enc_w3[2],
-                  d.enc_w3_inv[2], d.enc_b[2], d.x0, d.canon, d.act[1], d.act[2], d.act[3], s));
-  else if (enc_fused_head(d))
-    CHK(enc_head(d.fit, d.verts, d.V, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.enc_w3[1], d.enc_w3_inv[1], d.enc_b[1], d.x0, d.canon,
-                 d.act[1], d.act[2], s));
-  else
-    CHK(marker_c1(d.fit, d.verts, d.V, d.pose.Jtr, nj, d.transl, B, d.enc_w[0], d.enc_b[0], d.x0, d.canon, d.act[1], d.enc_ch[1], s));
-  CHK(enc_chain_fwd(d, H, W, s, enc_fused_head3(d) ? 3 : (enc_fused_head(d) ? 2 : 1)));
+  CHK(enc_head_fwd(d, d.V, H, W, s, 10));
   const double cnt = (double)d.enc_ch[10] * H * (W - 1);
   const float coef2 = (float)((double)d.weights_host[8] * 2.0 / cnt);
   CHK(smooth_loss(d.act[10], d.dact[0], nullptr, H, W, d.enc_ch[10], coef2, s, d.loss_acc + 32 * 32));
@@ -87,17 +76,11 @@ static int prox_iteration(const lemo_prox_desc& d, hipStream_t s, bool first) {
 }
 
 static int prox_capture(ProxEngine* e, hipStream_t s, int iters, hipGraphExec_t* out) {
-  hipGraph_t g = nullptr;
-  CHK((int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (int i = 0; i < iters && !rc; ++i) rc = prox_iteration(e->d, s, i == 0);
-  const int ec = (int)hipStreamEndCapture(s, &g);
-  if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-  CHK(ec);
-  const int ic = (int)hipGraphInstantiate(out, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (!ic) (void)hipGraphUpload(*out, s);
-  return ic;
+  return capture_graph(out, s, true, [&] {
+    int rc = 0;
+    for (int i = 0; i < iters && !rc; ++i) rc = prox_iteration(e->d, s, i == 0);
+    return rc;
+  });
 }
 
 extern "C" {
@@ -119,7 +102,7 @@ void* lemo_prox_create(const lemo_prox_desc* d) {
 void lemo_prox_destroy(void* h) {
   ProxEngine* e = (ProxEngine*)h;
   if (!e) return;
-  for (int l = 0; l < PROX_LEVELS; ++l) if (e->exec[l]) (void)hipGraphExecDestroy(e->exec[l]);
+  destroy_graphs(e->exec, PROX_LEVELS);
   delete e;
 }
 
@@ -154,23 +137,12 @@ int lemo_prox_step(void* h, int n, int use_graph, void* stream) {
 static int prox_state_io(ProxEngine* e, const lemo_prox_state* st, bool load, hipStream_t s) {
   if (!e || !st || !st->adam_m || !st->adam_v || !st->step) return LEMO_ERR_ARG;
   const lemo_prox_desc& d = e->d;
-  StateCopy a{};
   float* eng[11] = {d.global_orient, d.transl, d.left_hand_pose, d.right_hand_pose, d.jaw_pose, d.leye_pose, d.reye_pose,
                     d.expression, d.pose_embedding, d.adam_m, d.adam_v};
   float* usr[11] = {st->global_orient, st->transl, st->left_hand_pose, st->right_hand_pose, st->jaw_pose, st->leye_pose,
                     st->reye_pose, st->expression, st->pose_embedding, st->adam_m, st->adam_v};
   const int width[11] = {3, 3, 12, 12, 3, 3, 3, 10, 32, 81, 81};
-  for (int i = 0; i < 11; ++i) {
-    if (!eng[i] || !usr[i]) return LEMO_ERR_ARG;
-    a.src[i] = load ? usr[i] : eng[i];
-    a.dst[i] = load ? eng[i] : usr[i];
-    a.n[i] = d.B * width[i];
-  }
-  a.njobs = 11;
-  a.step_src = load ? st->step : d.step_ctr;
-  a.step_dst = load ? d.step_ctr : st->step;
-  a.nonfinite = load ? d.nonfinite : nullptr;
-  return state_copy(a, s);
+  return state_io(eng, usr, width, 11, d.B, d.step_ctr, st->step, d.nonfinite, load, s);
 }
 int lemo_prox_load_state(void* h, const lemo_prox_state* st, void* stream) { return prox_state_io((ProxEngine*)h, st, true, S(stream)); }
 int lemo_prox_save_state(void* h, const lemo_prox_state* st, void* stream) { return prox_state_io((ProxEngine*)h, st, false, S(stream)); }

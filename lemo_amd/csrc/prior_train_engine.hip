@@ -102,61 +102,59 @@ static bool sp_shape_ok(int H, int W, int bs) {
   return H >= 2 && W >= 2 && W <= 139 && bs >= 1 && bs <= 4096 && (long long)H * W <= (1ll << 20);
 }
 
-#define SP_CHK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
-
 // forward (+ losses); train: also the backward, Adam and the repack
 static int sp_run(SpEngine* e, hipStream_t s, bool train) {
   const int H = e->H, W = e->W, bs = e->bs;
   const size_t is = e->is, i1 = e->i1;
   const float* th = e->theta;
-  SP_CHK(sp_pad(e->xin, e->x0, bs, H, W, s));
-  for (int b = 0; b < bs; ++b) SP_CHK(conv3x3_c1(e->x0 + b * i1, th + e->enc[0].w_off, th + e->enc[0].b_off, e->act[1] + b * is, H, W, 32, s));
+  CHK(sp_pad(e->xin, e->x0, bs, H, W, s));
+  for (int b = 0; b < bs; ++b) CHK(conv3x3_c1(e->x0 + b * i1, th + e->enc[0].w_off, th + e->enc[0].b_off, e->act[1] + b * is, H, W, 32, s));
   for (int l = 1; l < 10; ++l) {
     const SpLayer& L = e->enc[l];
     for (int b = 0; b < bs; ++b)
-      SP_CHK(conv3x3_mfma_lds(e->act[l] + b * is, L.fwt, L.fwt2, th + L.b_off, nullptr, e->act[l + 1] + b * is, H, W, L.cin, L.cout, 0, s));
+      CHK(conv3x3_mfma_lds(e->act[l] + b * is, L.fwt, L.fwt2, th + L.b_off, nullptr, e->act[l + 1] + b * is, H, W, L.cin, L.cout, 0, s));
   }
   for (int j = 0; j < 8; ++j) {
     const SpLayer& L = e->dec[j];
     const float* din = j ? e->dout[j - 1] : e->act[10];
     for (int b = 0; b < bs; ++b)
-      SP_CHK(conv3x3_mfma_lds(din + b * is, L.fwt, L.fwt2, th + L.b_off, nullptr, e->dout[j] + b * is, H, W, L.cin, L.cout, 0, s));
+      CHK(conv3x3_mfma_lds(din + b * is, L.fwt, L.fwt2, th + L.b_off, nullptr, e->dout[j] + b * is, H, W, L.cin, L.cout, 0, s));
   }
   const double n_rec = (double)bs * H * W, n_sm = (double)bs * 64 * H * (W - 1);
-  SP_CHK(dec_end_fwd(e->dout[7], is, th + e->dec[8].w_off, th + e->dec[8].b_off, th + e->dec[9].w_off, th + e->dec[9].b_off, e->r1, e->rec,
+  CHK(dec_end_fwd(e->dout[7], is, th + e->dec[8].w_off, th + e->dec[8].b_off, th + e->dec[9].w_off, th + e->dec[9].b_off, e->r1, e->rec,
                      e->x0, train ? e->drec : nullptr, (float)(e->w_rec / n_rec), e->lpart, train ? e->ctr : nullptr, e->lr, bs, H, W, s));
   const float coef2 = (float)(2.0 * e->w_smooth / n_sm);
-  for (int b = 0; b < bs; ++b) SP_CHK(smooth_loss(e->act[10] + b * is, e->P[2] + b * is, e->spart + (size_t)b * e->nsp, H, W, 64, coef2, s));
-  SP_CHK(sp_losses(e->lpart, e->nl, e->spart, bs * e->nsp, n_rec, n_sm, e->w_rec, e->w_smooth, e->losses, s));
+  for (int b = 0; b < bs; ++b) CHK(smooth_loss(e->act[10] + b * is, e->P[2] + b * is, e->spart + (size_t)b * e->nsp, H, W, 64, coef2, s));
+  CHK(sp_losses(e->lpart, e->nl, e->spart, bs * e->nsp, n_rec, n_sm, e->w_rec, e->w_smooth, e->losses, s));
   if (!train) return 0;
 
   // ---- Dec backward
   float* g = e->grad;
-  SP_CHK(dec_end_bwd(e->drec, th + e->dec[9].w_off, e->r1, e->dpre8, th + e->dec[8].w_off, e->dout[7], is, e->P[0], bs, H, W, s));
-  SP_CHK(wgrad3x3_batched(e->r1, i1, e->drec, i1, bs, H, W, 1, 1, 1, e->wsg, g + e->dec[9].w_off, g + e->dec[9].b_off, s));
-  SP_CHK(wgrad3x3_batched(e->dout[7], is, e->dpre8, i1, bs, H, W, 32, 1, 1, e->wsg, g + e->dec[8].w_off, g + e->dec[8].b_off, s));
+  CHK(dec_end_bwd(e->drec, th + e->dec[9].w_off, e->r1, e->dpre8, th + e->dec[8].w_off, e->dout[7], is, e->P[0], bs, H, W, s));
+  CHK(wgrad3x3_batched(e->r1, i1, e->drec, i1, bs, H, W, 1, 1, 1, e->wsg, g + e->dec[9].w_off, g + e->dec[9].b_off, s));
+  CHK(wgrad3x3_batched(e->dout[7], is, e->dpre8, i1, bs, H, W, 32, 1, 1, e->wsg, g + e->dec[8].w_off, g + e->dec[8].b_off, s));
   float *cur = e->P[0], *oth = e->P[1];
   for (int j = 7; j >= 0; --j) {
     const SpLayer& L = e->dec[j];
     const float* din = j ? e->dout[j - 1] : e->act[10];
     for (int b = 0; b < bs; ++b)                 // d(input) * lrelu'(input): the input is the previous layer's (or Enc's) activation
-      SP_CHK(conv3x3_mfma_lds(cur + b * is, L.bwt, L.bwt2, nullptr, din + b * is, oth + b * is, H, W, L.cout, L.cin, 1, s));
-    SP_CHK(wgrad3x3_batched(din, is, cur, is, bs, H, W, L.cin, L.cout, 1, e->wsg, g + L.w_off, g + L.b_off, s));
+      CHK(conv3x3_mfma_lds(cur + b * is, L.bwt, L.bwt2, nullptr, din + b * is, oth + b * is, H, W, L.cout, L.cin, 1, s));
+    CHK(wgrad3x3_batched(din, is, cur, is, bs, H, W, L.cin, L.cout, 1, e->wsg, g + L.w_off, g + L.b_off, s));
     float* t = cur; cur = oth; oth = t;
   }
   // ---- d(pre-activation of Enc layer 9) = smoothness term (P[2], written by smooth_loss) + Dec's d z * lrelu'(z) (cur)
-  SP_CHK(sp_add(e->P[2], cur, (size_t)bs * is, s));
+  CHK(sp_add(e->P[2], cur, (size_t)bs * is, s));
   cur = e->P[2];
   for (int l = 9; l >= 1; --l) {
     const SpLayer& L = e->enc[l];
     for (int b = 0; b < bs; ++b)
-      SP_CHK(conv3x3_mfma_lds(cur + b * is, L.bwt, L.bwt2, nullptr, e->act[l] + b * is, oth + b * is, H, W, L.cout, L.cin, 1, s));
-    SP_CHK(wgrad3x3_batched(cur, is, e->act[l], is, bs, H, W, L.cout, L.cin, 0, e->wsg, g + L.w_off, g + L.b_off, s));
+      CHK(conv3x3_mfma_lds(cur + b * is, L.bwt, L.bwt2, nullptr, e->act[l] + b * is, oth + b * is, H, W, L.cout, L.cin, 1, s));
+    CHK(wgrad3x3_batched(cur, is, e->act[l], is, bs, H, W, L.cout, L.cin, 0, e->wsg, g + L.w_off, g + L.b_off, s));
     float* t = cur; cur = oth; oth = t;
   }
-  SP_CHK(wgrad3x3_batched(cur, is, e->x0, i1, bs, H, W, 32, 1, 0, e->wsg, g + e->enc[0].w_off, g + e->enc[0].b_off, s));
+  CHK(wgrad3x3_batched(cur, is, e->x0, i1, bs, H, W, 32, 1, 0, e->wsg, g + e->enc[0].w_off, g + e->enc[0].b_off, s));
   // ---- update
-  SP_CHK(sp_adam(e->theta, e->m, e->v, g, e->ctr, e->n_param, s));
+  CHK(sp_adam(e->theta, e->m, e->v, g, e->ctr, e->n_param, s));
   return sp_repack(e->pk, e->theta, s);
 }
 
@@ -171,8 +169,8 @@ static int sp_epoch_block(const SpEngine* e, const lemo_sptrain_epoch_desc* d, E
 }
 
 static int sp_epoch_step(SpEngine* e, bool train, hipStream_t s) {
-  SP_CHK(sp_assemble(EpochBlock{}, sp_block(e), 0, e->xin, e->bs, e->H, e->W, s));
-  SP_CHK(sp_run(e, s, train));
+  CHK(sp_assemble(EpochBlock{}, sp_block(e), 0, e->xin, e->bs, e->H, e->W, s));
+  CHK(sp_run(e, s, train));
   return ep_end(sp_block(e), e->losses, 3, s);
 }
 
@@ -214,8 +212,8 @@ void* lemo_sptrain_create(const lemo_sptrain_desc* d) {
 void lemo_sptrain_destroy(void* h) {
   SpEngine* e = (SpEngine*)h;
   if (!e) return;
-  if (e->exec) (void)hipGraphExecDestroy(e->exec);
-  for (int k = 0; k < 2; ++k) if (e->exec_ep[k]) (void)hipGraphExecDestroy(e->exec_ep[k]);
+  destroy_graphs(&e->exec, 1);
+  destroy_graphs(e->exec_ep, 2);
   delete e;
 }
 
@@ -224,11 +222,11 @@ int lemo_sptrain_load(void* h, const float* flat, void* stream) {
   if (!e || !flat) return LEMO_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)e->n_param;
-  SP_CHK((int)hipMemcpyAsync(e->theta, flat, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  SP_CHK((int)hipMemsetAsync(e->m, 0, sizeof(float) * n, s));          // a fresh optimizer
-  SP_CHK((int)hipMemsetAsync(e->v, 0, sizeof(float) * n, s));
-  SP_CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
-  SP_CHK(sp_repack(e->pk, e->theta, s));
+  CHK((int)hipMemcpyAsync(e->theta, flat, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemsetAsync(e->m, 0, sizeof(float) * n, s));          // a fresh optimizer
+  CHK((int)hipMemsetAsync(e->v, 0, sizeof(float) * n, s));
+  CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
+  CHK(sp_repack(e->pk, e->theta, s));
   e->loaded = 1;
   return 0;
 }
@@ -239,26 +237,16 @@ int lemo_sptrain_step(void* h, const float* x, int n, float* losses, void* strea
   if (!e || !x || n < 0) return LEMO_ERR_ARG;
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
-  SP_CHK((int)hipMemcpyAsync(e->xin, x, sizeof(float) * e->bs * e->H * e->W, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemcpyAsync(e->xin, x, sizeof(float) * e->bs * e->H * e->W, hipMemcpyDeviceToDevice, s));
   for (int i = 0; i < n; ++i) {
     if (e->use_graph) {
-      if (!e->exec) {
-        hipGraph_t g = nullptr;
-        SP_CHK((int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = sp_run(e, s, true);
-        const int ec = (int)hipStreamEndCapture(s, &g);
-        if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-        if (ec) return ec;
-        const int ic = (int)hipGraphInstantiate(&e->exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (ic) { e->exec = nullptr; return ic; }
-      }
-      SP_CHK((int)hipGraphLaunch(e->exec, s));
+      if (!e->exec) CHK(capture_graph(&e->exec, s, false, [&] { return sp_run(e, s, true); }));
+      CHK((int)hipGraphLaunch(e->exec, s));
     } else {
-      SP_CHK(sp_run(e, s, true));
+      CHK(sp_run(e, s, true));
     }
   }
-  if (losses) SP_CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 3, hipMemcpyDeviceToDevice, s));
+  if (losses) CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 3, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
@@ -268,10 +256,10 @@ int lemo_sptrain_eval(void* h, const float* x, float* losses, float* rec, void* 
   if (!e || !x || !losses) return LEMO_ERR_ARG;
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
-  SP_CHK((int)hipMemcpyAsync(e->xin, x, sizeof(float) * e->bs * e->H * e->W, hipMemcpyDeviceToDevice, s));
-  SP_CHK(sp_run(e, s, false));
-  SP_CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 3, hipMemcpyDeviceToDevice, s));
-  if (rec) SP_CHK((int)hipMemcpyAsync(rec, e->rec, sizeof(float) * e->bs * e->i1, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemcpyAsync(e->xin, x, sizeof(float) * e->bs * e->H * e->W, hipMemcpyDeviceToDevice, s));
+  CHK(sp_run(e, s, false));
+  CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 3, hipMemcpyDeviceToDevice, s));
+  if (rec) CHK((int)hipMemcpyAsync(rec, e->rec, sizeof(float) * e->bs * e->i1, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
@@ -293,15 +281,15 @@ int lemo_sptrain_epoch(void* h, const lemo_sptrain_epoch_desc* d, void* stream) 
   SpEngine* e = (SpEngine*)h;
   if (!e || !d || !d->log) return LEMO_ERR_ARG;
   EpochBlock B;
-  SP_CHK(sp_epoch_block(e, d, &B));
+  CHK(sp_epoch_block(e, d, &B));
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const bool train = d->train != 0;
-  SP_CHK(ep_begin(B, sp_block(e), s));
-  if (e->use_graph) SP_CHK(capture_chain(&e->exec_ep[train], s, [&] { return sp_epoch_step(e, train, s); }));
+  CHK(ep_begin(B, sp_block(e), s));
+  if (e->use_graph && !e->exec_ep[train]) CHK(capture_graph(&e->exec_ep[train], s, false, [&] { return sp_epoch_step(e, train, s); }));
   for (int i = 0; i < d->n_steps; ++i) {
-    if (e->use_graph) SP_CHK((int)hipGraphLaunch(e->exec_ep[train], s));
-    else SP_CHK(sp_epoch_step(e, train, s));
+    if (e->use_graph) CHK((int)hipGraphLaunch(e->exec_ep[train], s));
+    else CHK(sp_epoch_step(e, train, s));
   }
   return 0;
 }
@@ -310,7 +298,7 @@ int lemo_sptrain_batch(void* h, const lemo_sptrain_epoch_desc* d, int step, floa
   SpEngine* e = (SpEngine*)h;
   if (!e || !x) return LEMO_ERR_ARG;
   EpochBlock B;
-  SP_CHK(sp_epoch_block(e, d, &B));
+  CHK(sp_epoch_block(e, d, &B));
   if (step < 0 || step >= d->n_steps) return LEMO_ERR_ARG;
   return sp_assemble(B, nullptr, step, x, e->bs, e->H, e->W, (hipStream_t)stream);
 }
@@ -323,9 +311,9 @@ int lemo_sptrain_state_save(void* h, float* out, void* stream) {
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)e->n_param;
-  SP_CHK((int)hipMemcpyAsync(out, e->theta, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  SP_CHK((int)hipMemcpyAsync(out + n, e->m, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  SP_CHK((int)hipMemcpyAsync(out + 2 * n, e->v, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemcpyAsync(out, e->theta, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemcpyAsync(out + n, e->m, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemcpyAsync(out + 2 * n, e->v, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
   return train_step_counter(e->ctr, out + 3 * n, true, s);
 }
 
@@ -334,12 +322,12 @@ int lemo_sptrain_state_load(void* h, const float* in, void* stream) {
   if (!e || !in) return LEMO_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)e->n_param;
-  SP_CHK((int)hipMemcpyAsync(e->theta, in, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  SP_CHK((int)hipMemcpyAsync(e->m, in + n, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  SP_CHK((int)hipMemcpyAsync(e->v, in + 2 * n, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-  SP_CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
-  SP_CHK(train_step_counter(e->ctr, const_cast<float*>(in) + 3 * n, false, s));
-  SP_CHK(sp_repack(e->pk, e->theta, s));
+  CHK((int)hipMemcpyAsync(e->theta, in, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemcpyAsync(e->m, in + n, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemcpyAsync(e->v, in + 2 * n, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+  CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
+  CHK(train_step_counter(e->ctr, const_cast<float*>(in) + 3 * n, false, s));
+  CHK(sp_repack(e->pk, e->theta, s));
   e->loaded = 1;
   return 0;
 }

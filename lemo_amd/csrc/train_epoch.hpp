@@ -3,6 +3,7 @@
 // blob (train_epoch_kernels.hip).
 #pragma once
 #include "kernels.hpp"
+#include "engine_host.hpp"
 
 namespace lemo {
 
@@ -32,21 +33,5 @@ int aet_assemble_api(const EpochBlock& B, int step, float* x, float* y, int bs, 
 int sp_assemble(const EpochBlock& B, const EpochBlock* dev, int step, float* x, int bs, int H, int W, hipStream_t s);
 // Adam's step counter (ctr[0], an int) <-> two floats of a state blob: {step mod 2^24, step div 2^24}, both exact in fp32
 int train_step_counter(float* ctr, float* blob, bool save, hipStream_t s);
-
-// capture body() on s into *exec once (a single chain of kernel nodes)
-template <class F>
-static int capture_chain(hipGraphExec_t* exec, hipStream_t s, F&& body) {
-  if (*exec) return 0;
-  hipGraph_t g = nullptr;
-  if (int bc = (int)hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal)) return bc;
-  const int rc = body();
-  const int ec = (int)hipStreamEndCapture(s, &g);
-  if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-  if (ec) return ec;
-  const int ic = (int)hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (ic) *exec = nullptr;
-  return ic;
-}
 
 }  // namespace lemo

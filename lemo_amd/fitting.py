@@ -19,9 +19,10 @@ import numpy as np
 import torch
 
 from . import _hip
+from ._engine import NativeEngine, state_tensors
 from ._hip import ptr
 from .body_model import BodyModelData, DeviceBody, alloc_pose_ws, K_PAD, load_model_dict
-from .priors import DEFAULT_CONV_VARIANT, ENC_CHANNELS, EncWeights, cg8p_alloc
+from .priors import ENC_CHANNELS, EncWeights, alloc_enc_maps, clamp_conv_variant, warn_if_wide_image
 from .rotation import convert_to_6D_all
 from .vposer import vposer_weight_struct
 
@@ -36,7 +37,9 @@ DEFAULT_SIDE_FULL_FORWARD = __import__('os').environ.get('LEMO_SIDE_FULL_FORWARD
 """all-vertex forward on the engine's side stream (AmassTemporalFitter.side_full_forward); the environment switch exists for A/B runs"""
 
 
-class AmassTemporalFitter(_hip.StreamOrdered):
+class AmassTemporalFitter(NativeEngine):
+    _destroy = 'fit_destroy'
+
     def __init__(self, body, vposer_weights: Dict[str, np.ndarray], enc_state: Dict[str, np.ndarray],
                  ids: Dict[str, np.ndarray], Xmean: np.ndarray, Xstd: np.ndarray, B: int, device,
                  weights: Optional[dict] = None, full_vertices: bool = True, num_pca_comps: int = 12,
@@ -128,31 +131,15 @@ class AmassTemporalFitter(_hip.StreamOrdered):
                        dx0=z(H * W), spartial=z(nsp), vpartial=z(B, 9), losses=z(12), dverts=z(B, n, 3),
                        dvp=z(B, uset.NCs), dA=z(B, nj, 12), dX=z(B, K_PAD),
                        g_transl=z(B, 3), g_rot6d=z(B, 6), g_other=z(B, 56), g_go=z(B, 3), g_body=z(B, 63))
-        self.act = [None] + [cg8p_alloc(ENC_CHANNELS[l], H, W, dev) for l in range(1, 11)]
-        self.dact = [cg8p_alloc(64, H, W, dev), cg8p_alloc(64, H, W, dev)]
 
         d = _hip.FitDesc()
         d.B, d.Bp, d.V, d.nrows, d.full_vertices = B, Bp, data.V, self.nrows, int(self.full)
-        if conv_variant is None:
-            conv_variant = DEFAULT_CONV_VARIANT
-        if int(conv_variant) in (2, 3, 4) and 127 + 2 * (127 // self.W + 1) + 2 * (self.W + 2) + 3 > 416:
-            conv_variant = 1                      # LDS tile of variant 2 holds W <= 139 (B <= 124); the single-layer split kernels W <= 134
-        # (variant 5 stays: the fused pairs take any width -- 12 of the 14 64 -> 64 layers; the engine sends the other launches to the
-        # fp32-input kernel layer by layer, lemo_amd/csrc/enc_chain.hpp::enc_layer.  Round 4: all 18 launches used to fall back.)
-        from .priors import check_conv_variant
-        self.conv_variant = d.conv_variant = check_conv_variant(conv_variant)
+        self.conv_variant = d.conv_variant = clamp_conv_variant(conv_variant, W)
         if not self.per_frame:
-            from .priors import warn_if_wide_image
             warn_if_wide_image(self.lib, H, W, self.conv_variant)
         d.vposer, d.body, d.skin, d.uset, d.fit = self.vposer_struct, self.dev.body, self.dev.skin, uset, fit
         d.fwd_ids = ptr(I['fwd_ids'])
-        for i, c in enumerate(ENC_CHANNELS): d.enc_ch[i] = c
-        for l in range(10):
-            d.enc_w[l], d.enc_b[l], d.enc_wbwd[l] = ptr(self.enc.w[l]), ptr(self.enc.b[l]), ptr(self.enc.wbwd[l])
-            d.enc_w2[l], d.enc_wbwd2[l] = ptr(self.enc.w2[l]), ptr(self.enc.wbwd2[l])
-            for bwd, dst, dinv in ((False, d.enc_w3, d.enc_w3_inv), (True, d.enc_wbwd3, d.enc_wbwd3_inv)):
-                pack, winv = self.enc.split_pack(l, bwd, self.conv_variant)         # bf16 x 3 (variant 3) or f16 x 2 (variant 4)
-                dst[l], dinv[l] = (ptr(pack) if pack is not None else None), float(winv)
+        self.enc.fill_desc(d, self.conv_variant)
         d.target, d.contact, d.weights = ptr(self.target), ptr(self.contact), ptr(self._w_dev)
         for i, v in enumerate(wl): d.weights_host[i] = v
         d.transl, d.rot6d, d.other, d.shape = (ptr(self.P[k]) for k in ('transl', 'rot6d', 'other', 'shape'))
@@ -172,8 +159,7 @@ class AmassTemporalFitter(_hip.StreamOrdered):
         if self.side_full:
             self.ws['verts_side'], self.ws['transl_side'] = z(B, data.V, 3), z(B, 3)
             d.verts_side, d.transl_side = ptr(self.ws['verts_side']), ptr(self.ws['transl_side'])
-        for l in range(1, 11): d.act[l] = ptr(self.act[l])
-        d.dact[0], d.dact[1] = ptr(self.dact[0]), ptr(self.dact[1])
+        self.act, self.dact = alloc_enc_maps(d, H, W, dev)
         self.desc = d
         self.handle = self.lib.fit_create(C.byref(d))
         if not self.handle:
@@ -203,17 +189,6 @@ class AmassTemporalFitter(_hip.StreamOrdered):
         s.wait_stream(self._cur())
         with torch.cuda.stream(s):
             self.step(n, use_graph=use_graph)
-
-    def __del__(self):
-        h, self.handle = getattr(self, 'handle', None), None
-        if h:
-            # The engine's buffers are torch tensors allocated on the default stream but written by graph replays on whatever
-            # stream step() ran on.  When the last reference goes, the caching allocator may hand those blocks to the next
-            # default-stream allocation at once -- while a replay is still in flight they would be written from two places.
-            lib, rel = self.lib, getattr(_hip, 'release', None) if _hip is not None else None
-            if rel is None:                  # interpreter shutdown: module globals are gone, the process is about to exit
-                return
-            rel(self.device, lib, lambda: lib.fit_destroy(h), getattr(self, '_run_ev', None))
 
     # -- sequence setup (opt_amass_temp.py:332-345) -------------------------------------------
     @torch.no_grad()
@@ -274,12 +249,7 @@ class AmassTemporalFitter(_hip.StreamOrdered):
         """continue from ``state`` (the dict :meth:`save_state` returns; numpy arrays or tensors, ``step`` an int or a
         tensor): the next :meth:`step` is iteration ``step`` of the loop -- learning-rate level, bias corrections and all.
         Sequence data (``target``, ``contact``, ``shape``) are not part of the optimiser state: :meth:`load_sequence` first."""
-        td = lambda a, w: (a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32))
-                           ).to(self.device, torch.float32).reshape(self.B, w).contiguous()
-        t = {k: td(state[k], w) for k, w in zip(self.STATE_KEYS, (3, 6, 56) * 3)}
-        sv = state['step']
-        step = (sv.detach().to(self.device, torch.int32).reshape(1) if isinstance(sv, torch.Tensor)
-                else torch.full((1,), int(sv), dtype=torch.int32, device=self.device))
+        t, step = state_tensors(state, tuple(zip(self.STATE_KEYS, (3, 6, 56) * 3)), self.B, self.device)
         self._before_run()
         self.lib.check(self.lib.fit_load_state(self.handle, C.byref(self._state_struct(t, step)), self._s()), 'fit_load_state')
         self._stepped = False
@@ -287,11 +257,6 @@ class AmassTemporalFitter(_hip.StreamOrdered):
         self._keep = (t, step)              # the copies read caller-side buffers asynchronously: keep them until the next call
 
     # -- execution ---------------------------------------------------------------------------
-    def _s(self):
-        if self.lib.is_emu:
-            return None
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def forward(self) -> None:
         self._before_run()
         self.lib.check(self.lib.fit_forward(self.handle, self._s()), 'fit_forward')

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
+from ._engine import release_on_del
 from ._hip import ptr
 from .priors import cg8p_alloc, from_cg8p, to_cg8p
 
@@ -449,12 +450,11 @@ class _FinetuneSession:
         import contextlib
         return torch.cuda.stream(self.stream) if self.gpu else contextlib.nullcontext()
 
-    def __del__(self):
+    def __del__(self, _release=release_on_del):
         exe, self.exe = getattr(self, 'exe', None), None
         if exe is not None:
-            lib, rel = self.lib, getattr(_hip, 'release', None) if _hip is not None else None
-            if rel is not None:              # (None: interpreter shutdown)
-                rel(self.device, lib, lambda: lib.graph_destroy(exe))
+            lib = self.lib
+            _release(self.device, lib, lambda: lib.graph_destroy(exe))
 
     def train_step(self):
         # loss = (|rec - x| * m).sum() / cnt (opt_amass_temp.py:199-203); its gradient is closed-form, so the eleven small
@@ -543,14 +543,14 @@ class _EngineSession:
             raise _hip.LemoHipError('lemo_ae_create failed')
         self._ev = None
 
-    def __del__(self):
+    def __del__(self, _release=release_on_del):
         h, self.h = getattr(self, 'h', None), None
         if h:
-            lib, rel = self.lib, getattr(_hip, 'release', None) if _hip is not None else None
-            if rel is not None:              # (None: interpreter shutdown)
-                def destroy(h=h, ws=self.ws):            # (the workspace outlives the engine's last launch)
-                    lib.ae_destroy(h)
-                rel(self.device, lib, destroy, self._ev)
+            lib = self.lib
+
+            def destroy(h=h, ws=self.ws):                # (the workspace outlives the engine's last launch)
+                lib.ae_destroy(h)
+            _release(self.device, lib, destroy, self._ev)
 
     def _s(self):
         return self.stream.cuda_stream if self.gpu else None

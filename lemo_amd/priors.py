@@ -208,6 +208,26 @@ class EncWeights:
                     self.w10.append(None); self.wbwd10.append(None); self.w10_inv.append(1.0); self.wbwd10_inv.append(1.0)
             self.b.append(t(b))
 
+    def fill_desc(self, d, variant: int) -> None:
+        """the ``enc_*`` fields of a ``lemo_fit_desc`` / ``lemo_prox_desc``: channel counts and every layer's packs for ``variant``"""
+        for i, c in enumerate(ENC_CHANNELS): d.enc_ch[i] = c
+        for l in range(10):
+            d.enc_w[l], d.enc_b[l], d.enc_wbwd[l] = ptr(self.w[l]), ptr(self.b[l]), ptr(self.wbwd[l])
+            d.enc_w2[l], d.enc_wbwd2[l] = ptr(self.w2[l]), ptr(self.wbwd2[l])
+            for bwd, dst, dinv in ((False, d.enc_w3, d.enc_w3_inv), (True, d.enc_wbwd3, d.enc_wbwd3_inv)):
+                pack, winv = self.split_pack(l, bwd, variant)         # bf16 x 3 (variant 3) or f16 x 2 (variant 4)
+                dst[l], dinv[l] = (ptr(pack) if pack is not None else None), float(winv)
+
+
+def alloc_enc_maps(d, H: int, W: int, dev):
+    """the encoder's activation maps act[1..10] and the two ping-pong gradient maps dact[0..1] of an H x W image, wired into the
+    descriptor ``d``; returns ``(act, dact)`` (act[0] is None: layer 0 reads the padded image x0)"""
+    act = [None] + [cg8p_alloc(ENC_CHANNELS[l], H, W, dev) for l in range(1, 11)]
+    dact = [cg8p_alloc(64, H, W, dev), cg8p_alloc(64, H, W, dev)]
+    for l in range(1, 11): d.act[l] = ptr(act[l])
+    d.dact[0], d.dact[1] = ptr(dact[0]), ptr(dact[1])
+    return act, dact
+
 
 # ----------------------------------------------------------------------------------------------
 # Encoder as autograd ops over the C ABI
@@ -237,6 +257,22 @@ def check_conv_variant(v: int) -> int:
     return v
 
 
+def lds_tile_fits(W: int, limit: int = 416) -> bool:
+    """a 1-D tile of 128 pixels with its two halo rows fits the `limit` staged pixels of the LDS-tiled kernels: 416 for
+    conv3x3_mfma_lds (W <= 139, B <= 124), 408 for the single-layer split kernels (conv_split_kernels.hip CV3_NPX: W <= 134)"""
+    return 127 + 2 * (127 // W + 1) + 2 * (W + 2) + 3 <= limit
+
+
+def clamp_conv_variant(v, W: int) -> int:
+    """the conv variant an engine runs an image of width W with: None = ``DEFAULT_CONV_VARIANT``; 2, 3, 4 need the LDS tile and
+    become 1 where it does not fit (5 and up stay: the fused pairs take any width -- 12 of the 14 64 -> 64 layers; the engine
+    sends the other launches to the fp32-input kernel layer by layer, csrc/enc_chain.hpp::enc_layer)"""
+    v = DEFAULT_CONV_VARIANT if v is None else int(v)
+    if v in (2, 3, 4) and not lds_tile_fits(W):
+        v = 1
+    return check_conv_variant(v)
+
+
 def _conv_layer(lib, enc: EncWeights, l: int, bwd: bool, x, out, aux, H, W, variant, s):
     """one MFMA layer (forward: epi 0 with bias; backward-data: epi 1 with the saved activation) on the best
     kernel family `variant` allows for its shape"""
@@ -252,7 +288,7 @@ def _conv_layer(lib, enc: EncWeights, l: int, bwd: bool, x, out, aux, H, W, vari
         lib.check(lib.conv3x3_mfma_split_f16(ptr(x), ptr(w4), winv, ptr(wt), bias, auxp, ptr(out), H, W, cin, cout, epi, s), 'conv3x3_mfma_split_f16')
     elif variant >= 3 and w3 is not None and lib.conv3x3_split_supported(H, W, cin, cout):
         lib.check(lib.conv3x3_mfma_split(ptr(x), ptr(w3), ptr(wt), bias, auxp, ptr(out), H, W, cin, cout, epi, s), 'conv3x3_mfma_split')
-    elif variant >= 2 and 127 + 2 * (127 // W + 1) + 2 * (W + 2) + 3 <= 416:
+    elif variant >= 2 and lds_tile_fits(W):
         lib.check(lib.conv3x3_mfma_lds(ptr(x), ptr(wt), ptr(wt2), bias, auxp, ptr(out), H, W, cin, cout, epi, s), 'conv3x3_mfma_lds')
     else:
         lib.check(lib.conv3x3_mfma(ptr(x), ptr(wt), bias, auxp, ptr(out), H, W, cin, cout, epi, 1, s), 'conv3x3_mfma')
@@ -390,8 +426,7 @@ def warn_if_wide_image(lib, H: int, W: int, conv_variant: int) -> bool:
     238 frames where linear scaling from 119 would give ~1700).  Warn so that the slowdown is not silent; True when it applies."""
     import warnings
     H, W = int(H), int(W)
-    too_wide = 127 + 2 * (127 // W + 1) + 2 * (W + 2) + 3 > 408          # conv_split_kernels.hip: CV3_NPX staged pixels
-    if conv_variant >= 3 and H * W >= 128 and too_wide and not lib.conv3x3_split_supported(H, W, 64, 64):
+    if conv_variant >= 3 and H * W >= 128 and not lds_tile_fits(W, 408) and not lib.conv3x3_split_supported(H, W, 64, 64):
         warnings.warn(f'lemo_amd: smoothness image {H} x {W} is wider than the split-f16 single-layer kernels take (W <= 134, i.e. clips of '
                       f'up to 120 frames); the 32-channel layers and the unpaired 64 -> 64 layers run on the slower fp32-input kernels',
                       RuntimeWarning, stacklevel=3)

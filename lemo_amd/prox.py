@@ -23,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
+from ._engine import NativeEngine, state_tensors
 from .assets import asset_path
 from .body_model import SMPLX
 from .priors import Enc
@@ -376,12 +377,13 @@ ENGINE_PARAMS = (('global_orient', 3), ('transl', 3), ('left_hand_pose', 12), ('
 (fit_temp_loadprox_slide.py:511-519)."""
 
 
-class ProxWindowEngine(_hip.StreamOrdered):
+class ProxWindowEngine(NativeEngine):
     """One sliding window (B frames) of the PROX temporal fit on the native engine (``lemo_prox_*``): closure
     ``fitting_func`` (fitting_temp_slide.py:239-311), the S2 / S3-active ``SMPLifyLoss`` terms, backward, first-15 % erase
     and Adam (lr 0.005) are a fixed sequence of ~40 HIP kernels captured once and replayed -- no torch op, no host sync,
     no atomics-ordered accumulation (graph replay == eager launches bit for bit).  Same constructor as
     :class:`ProxTemporalFitter` (which stays as the module-level / autograd composition of the same kernels)."""
+    _destroy = 'prox_destroy'
 
     def __init__(self, body_model: SMPLX, vposer: VPoser, smooth_encoder: Enc, ids: Dict[str, np.ndarray], Xmean, Xstd,
                  weights: dict, R, t, sdf: torch.Tensor, grid_min, grid_max, params: Dict[str, np.ndarray], gt_joints,
@@ -391,7 +393,7 @@ class ProxWindowEngine(_hip.StreamOrdered):
         import ctypes as C
         from ._hip import ptr
         from .body_model import K_PAD, alloc_pose_ws
-        from .priors import DEFAULT_CONV_VARIANT, ENC_CHANNELS, EncWeights, cg8p_alloc
+        from .priors import EncWeights, alloc_enc_maps, clamp_conv_variant
         from .vposer import vposer_weight_struct
         self.lib = lib = body_model._lib_override or _hip.get_lib()
         dev = sdf.device
@@ -497,25 +499,13 @@ class ProxWindowEngine(_hip.StreamOrdered):
                        dX=z(B, K_PAD), g_go=z(B, 3), g_lh=z(B, 12), g_rh=z(B, 12), g_jaw=z(B, 3), g_leye=z(B, 3), g_reye=z(B, 3),
                        g_expr=z(B, 10), g_pe=z(B, 32), losses=z(16))
         self.loss_acc = torch.zeros(32 * 32 + 32 * 16, dtype=torch.float64, device=dev)
-        self.act = [None] + [cg8p_alloc(ENC_CHANNELS[l], H, W, dev) for l in range(1, 11)]
-        self.dact = [cg8p_alloc(64, H, W, dev), cg8p_alloc(64, H, W, dev)]
         self.sdf = sdf.contiguous().float()
         d = _hip.ProxDesc()
         d.B, d.Bp, d.V = B, Bp, V
-        cv = DEFAULT_CONV_VARIANT if conv_variant is None else int(conv_variant)
-        if cv in (2, 3, 4) and 127 + 2 * (127 // W + 1) + 2 * (W + 2) + 3 > 416:
-            cv = 1                                 # (variant 5 stays for wide windows: the fused pairs take any width, fitting.py)
-        from .priors import check_conv_variant
-        self.conv_variant = d.conv_variant = check_conv_variant(cv)
+        self.conv_variant = d.conv_variant = clamp_conv_variant(conv_variant, W)
         d.first_batch_flag, d.use_infill, d.T = int(bool(first_batch_flag)), int(self.use_infill), B - 1
         d.vposer, d.body, d.skin, d.uset, d.fit, d.pc = self.vposer_struct, self.dbody.body, self.dbody.skin, uset, fitc, pc
-        for i, c in enumerate(ENC_CHANNELS): d.enc_ch[i] = c
-        for l in range(10):
-            d.enc_w[l], d.enc_b[l], d.enc_wbwd[l] = ptr(self.enc.w[l]), ptr(self.enc.b[l]), ptr(self.enc.wbwd[l])
-            d.enc_w2[l], d.enc_wbwd2[l] = ptr(self.enc.w2[l]), ptr(self.enc.wbwd2[l])
-            for bwd, dst, dinv in ((False, d.enc_w3, d.enc_w3_inv), (True, d.enc_wbwd3, d.enc_wbwd3_inv)):
-                pack, winv = self.enc.split_pack(l, bwd, cv)                         # bf16 x 3 (variant 3) or f16 x 2 (variant 4)
-                dst[l], dinv[l] = (ptr(pack) if pack is not None else None), float(winv)
+        self.enc.fill_desc(d, self.conv_variant)
         d.sdf = ptr(self.sdf)
         for i in range(3):
             d.sdf_dim[i], d.grid_min[i], d.grid_max[i] = int(self.sdf.shape[i]), float(grid_min[i]), float(grid_max[i])
@@ -533,8 +523,7 @@ class ProxWindowEngine(_hip.StreamOrdered):
                   'dfp_add', 'dvp', 'dA', 'dtr_v', 'dX', 'g_go', 'g_lh', 'g_rh', 'g_jaw', 'g_leye', 'g_reye', 'g_expr', 'g_pe', 'losses'):
             setattr(d, k, ptr(self.ws[k]))
         d.pose = pose_ws
-        for l in range(1, 11): d.act[l] = ptr(self.act[l])
-        d.dact[0], d.dact[1] = ptr(self.dact[0]), ptr(self.dact[1])
+        self.act, self.dact = alloc_enc_maps(d, H, W, dev)
         d.loss_acc = ptr(self.loss_acc)
         self.desc = d
         self.handle = lib.prox_create(C.byref(d))
@@ -543,20 +532,6 @@ class ProxWindowEngine(_hip.StreamOrdered):
         self.first_batch_flag = bool(first_batch_flag)
         self._init_order(self.device, lib)
         self._after_write()          # the parameter copies above were enqueued on the constructor's current stream
-
-    def __del__(self):
-        h, self.handle = getattr(self, 'handle', None), None
-        if h:
-            # The engine's buffers are torch tensors allocated on the default stream but written by graph replays on whatever
-            # stream step() ran on.  When the last reference goes, the caching allocator may hand those blocks to the next
-            # default-stream allocation at once -- while a replay is still in flight they would be written from two places.
-            lib, rel = self.lib, getattr(_hip, 'release', None) if _hip is not None else None
-            if rel is None:                  # interpreter shutdown: module globals are gone, the process is about to exit
-                return
-            rel(self.device, lib, lambda: lib.prox_destroy(h), getattr(self, '_run_ev', None))
-
-    def _s(self):
-        return None if self.lib.is_emu else torch.cuda.current_stream(self.device).cuda_stream
 
     def closure(self) -> Dict[str, float]:
         """forward + backward (no update, no erase): fills the loss record and the gradient buffers"""
@@ -598,14 +573,8 @@ class ProxWindowEngine(_hip.StreamOrdered):
         """continue from ``state`` (see :meth:`save_state`; numpy or tensors; ``adam_m`` / ``adam_v`` / ``step`` default to a
         fresh optimiser -- what a new window starts with, data_parser_slide.py:326-331 + fit_temp_loadprox_slide.py:511-519)"""
         import ctypes as C
-        td = lambda a, w: (a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32))
-                           ).to(self.device, torch.float32).reshape(self.B, w).contiguous()
-        t = {k: td(state[k], d) for k, d in ENGINE_PARAMS}
-        for k in ('adam_m', 'adam_v'):
-            t[k] = td(state[k], 81) if state.get(k) is not None else torch.zeros(self.B, 81, dtype=torch.float32, device=self.device)
-        sv = state.get('step', 0)
-        t['step'] = (sv.detach().to(self.device, torch.int32).reshape(1) if isinstance(sv, torch.Tensor)
-                     else torch.full((1,), int(sv), dtype=torch.int32, device=self.device))
+        fresh = {k: torch.zeros(self.B, 81, dtype=torch.float32, device=self.device) for k in ('adam_m', 'adam_v') if state.get(k) is None}
+        t, t['step'] = state_tensors({'step': 0, **state, **fresh}, ENGINE_PARAMS + (('adam_m', 81), ('adam_v', 81)), self.B, self.device)
         self._before_run()
         self.lib.check(self.lib.prox_load_state(self.handle, C.byref(self._state_struct(t)), self._s()), 'prox_load_state')
         self._after_run()
