@@ -798,6 +798,78 @@ typedef struct lemo_prox_state {
 int lemo_prox_load_state(void* h, const lemo_prox_state* st, void* stream);
 int lemo_prox_save_state(void* h, const lemo_prox_state* st, void* stream);
 
+/* ---- optional terms of the PROX window engine (csrc/prox_terms_kernels.hip) ------------------------------------------------
+ * The terms cfg_files/PROXD_temp_S3.yaml:58-86 switches on top of the S2 / S3 set, as SMPLifyLoss.forward evaluates them: s2m / m2s
+ * :637-670, self-penetration :618-635, body-scene contact :743-753, marker acceleration / velocity :756-772.  lemo_prox_set_terms
+ * attaches them to a created engine: call it before the first step (a later call drops the captured graphs; the next step captures
+ * again).  A term whose weight is 0 or whose pointers are NULL launches nothing; an engine that never sees this call runs exactly the
+ * launches of lemo_prox_step above.  In an iteration the terms run behind prox_sparse and in front of the all-vertex backward, add
+ * their gradients to lemo_prox_desc.dverts (camera space), fill losses[2, 3, 4, 6, 7, 8] and add those to losses[0] in the order
+ * contact, s2m + m2s, self-penetration, acceleration, velocity, so the non-finite latch sees them.
+ * Everything below is caller-allocated device memory except contact_vid_host; the engine never allocates or synchronises.  The
+ * searches are the entry points further down (lemo_chamfer_forward with LEMO_CHAMFER_SHARED, lemo_vertex_visibility,
+ * lemo_chamfer_masked_forward twice, lemo_selfpen_search, lemo_selfpen_loss_forward), inside the capture; they see the iteration's
+ * vertices and take no gradient.  The workspaces have the sizes of those entry points' lemo_*_workspace_bytes functions for
+ * (B, Nc, M, SHARED, 0), (B, V, F, AUTO, 0), the larger of (B, S, V, 0, 0) and (B, V, S, 0, 0), and (B, V, F, AUTO, 0).
+ *   contact   scene_v [M][3] world space, contact_vid [Nc] with a host copy (unique ids in [0, V)): d = squared distance of
+ *             R v + t to the nearest scene vertex, s = sqrt(d + 1e-4), contact_loss_weight * mean(s / (s + 1)); the gradient goes
+ *             back through R^T to the one dverts row an id owns (no atomics).  Scratch: contact_xyz [B][Nc][3], contact_dist /
+ *             contact_idx [B][Nc], contact_ws.
+ *   scan      faces [F][3], scan [B][S][3] camera space, scan_point_num [B] (clamped to 0 .. S on the device), body_mask [V] bytes.
+ *             vis = lemo_vertex_visibility(verts, min_dist); a frame is live iff it has a scan point and a visible vertex (m2s: and a
+ *             vertex with vis & body_mask); per live frame the mean of rho^2 d / (d + rho^2) over the valid scan points against the
+ *             visible vertices (s2m) / over the vis & body_mask vertices against the valid scan points (m2s); weight * mean over the
+ *             live frames.  Scratch: vis, qmask [B][V] bytes, scan_counts [3][B], s2m_dist / s2m_idx [B][S], m2s_dist / m2s_idx
+ *             [B][V], vis_ws, scan_ws.
+ *   selfpen   faces, optional segm / parents [F] and ign [P][P] (as lemo_selfpen_search); sum over the frames of coll_loss_weight *
+ *             lemo_selfpen_loss_forward.  Scratch: pairs [B][max_pairs][2], pair_count [B], pen_loss [B], pen_ws.
+ *   velocity  the markers fit.row81 of the engine: smooth_vel_weight * mean((x[b+1] - x[b])^2) over (B - 1) n81 3 entries and
+ *             smooth_acc_weight * mean of the squared second difference over (B - 2) n81 3.
+ * The two scattered adjoints (s2m: many scan points share a vertex; self-penetration) are summed in fix_acc [B][V][3][2], fixed point
+ * in two 64-bit words per entry (units of 2^-20 and 2^-60, csrc/fixed_acc.hpp) with integer atomics: the sum does not depend on the
+ * order of arrival, so graph replay == eager launches bit for bit.  It is zeroed every iteration and added to dverts by the closing
+ * kernel.  A contribution that is not finite or not below 2^17 in magnitude is not converted, and neither is a valid scan point that
+ * is not finite: either raises fix_flag [1] and the closing kernel makes losses[0] NaN, which latches
+ * lemo_prox_desc.nonfinite.  frame_acc [B][8] (double): the per-frame sums behind the loss values.
+ * LEMO_ERR_ARG: a NULL handle or struct, a negative or non-finite weight, a live term with a NULL pointer or a workspace smaller than
+ * stated, contact ids that repeat or leave [0, V), rho / sigma that are not positive; LEMO_ERR_SHAPE: the limits of the entry points
+ * named above for the shapes given.  Nothing is launched and the engine keeps its earlier terms then. */
+typedef struct lemo_prox_terms {
+  /* contact */
+  const float* scene_v; int M;
+  const int* contact_vid; const int* contact_vid_host; int Nc;
+  float contact_loss_weight;
+  float* contact_xyz; float* contact_dist; int* contact_idx;
+  void* contact_ws; long long contact_ws_bytes;
+  /* the mesh (scan and self-penetration) */
+  const int* faces; int F;
+  /* scan */
+  const float* scan; int S;
+  const int* scan_point_num;
+  const unsigned char* body_mask;
+  float s2m_weight, m2s_weight, rho_s2m, rho_m2s, min_dist;
+  unsigned char *vis, *qmask;
+  int* scan_counts;
+  float* s2m_dist; int* s2m_idx;
+  float* m2s_dist; int* m2s_idx;
+  void* vis_ws; long long vis_ws_bytes;
+  void* scan_ws; long long scan_ws_bytes;
+  /* self-penetration */
+  const int *segm, *parents; const unsigned char* ign; int P;
+  float coll_loss_weight, sigma;
+  int penalize_outside, max_pairs;
+  int *pairs, *pair_count;
+  float* pen_loss;
+  void* pen_ws; long long pen_ws_bytes;
+  /* marker velocity / acceleration */
+  float smooth_acc_weight, smooth_vel_weight;
+  /* shared scratch */
+  long long* fix_acc;             /* [B][V][3][2]; needed with s2m or self-penetration */
+  int* fix_flag;                  /* [1] */
+  double* frame_acc;              /* [B][8] */
+} lemo_prox_terms;
+int lemo_prox_set_terms(void* h, const lemo_prox_terms* t);
+
 /* ---- occlusion masks (csrc/occlusion_kernels.hip): utils/get_occlusion_mask.py:111-147, 170-201 ----
  * Pinhole camera in camera space (y down, z forward): u = fx X / Z + cx, v = fy Y / Z + cy; pixel [y][x] samples the ray through
  * (x + 0.5, y + 0.5).  Depth is the camera-space Z of the nearest hit with znear <= Z <= zfar, 0 where nothing is hit.

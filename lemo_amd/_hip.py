@@ -207,6 +207,24 @@ class ProxState(C.Structure):
                                   'expression', 'pose_embedding', 'adam_m', 'adam_v', 'step')]
 
 
+class ProxTerms(C.Structure):
+    """lemo_prox_terms"""
+    _fields_ = [
+        ('scene_v', vp), ('M', C.c_int), ('contact_vid', vp), ('contact_vid_host', vp), ('Nc', C.c_int), ('contact_loss_weight', C.c_float),
+        ('contact_xyz', vp), ('contact_dist', vp), ('contact_idx', vp), ('contact_ws', vp), ('contact_ws_bytes', C.c_longlong),
+        ('faces', vp), ('F', C.c_int),
+        ('scan', vp), ('S', C.c_int), ('scan_point_num', vp), ('body_mask', vp),
+        ('s2m_weight', C.c_float), ('m2s_weight', C.c_float), ('rho_s2m', C.c_float), ('rho_m2s', C.c_float), ('min_dist', C.c_float),
+        ('vis', vp), ('qmask', vp), ('scan_counts', vp), ('s2m_dist', vp), ('s2m_idx', vp), ('m2s_dist', vp), ('m2s_idx', vp),
+        ('vis_ws', vp), ('vis_ws_bytes', C.c_longlong), ('scan_ws', vp), ('scan_ws_bytes', C.c_longlong),
+        ('segm', vp), ('parents', vp), ('ign', vp), ('P', C.c_int), ('coll_loss_weight', C.c_float), ('sigma', C.c_float),
+        ('penalize_outside', C.c_int), ('max_pairs', C.c_int), ('pairs', vp), ('pair_count', vp), ('pen_loss', vp),
+        ('pen_ws', vp), ('pen_ws_bytes', C.c_longlong),
+        ('smooth_acc_weight', C.c_float), ('smooth_vel_weight', C.c_float),
+        ('fix_acc', vp), ('fix_flag', vp), ('frame_acc', vp),
+    ]
+
+
 def ptr(t: Optional[torch.Tensor]):
     """raw device pointer of a contiguous tensor (None -> NULL)."""
     if t is None:
@@ -345,6 +363,7 @@ _SIGS = {
     'lemo_prox_destroy': (None, [vp]),
     'lemo_prox_closure': (C.c_int, [vp, vp]),
     'lemo_prox_step': (C.c_int, [vp, C.c_int, C.c_int, vp]),
+    'lemo_prox_set_terms': (C.c_int, [vp, C.POINTER(ProxTerms)]),
     'lemo_depth_raster': (C.c_int, [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(OcclCam), vp, vp]),
     'lemo_occlusion_query': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(OcclCam), C.c_float, C.c_float, vp, C.c_float,
                                        vp, vp, vp, vp, vp]),

@@ -10,6 +10,10 @@ int prox_frame_dense(const lemo_prox_desc& d, hipStream_t s);
 int prox_sparse(const lemo_prox_desc& d, double smooth_count, hipStream_t s);
 int prox_adam(const lemo_prox_desc& d, hipStream_t s);
 int prox_tail(const lemo_prox_desc& d, bool update, hipStream_t s);
+// prox_terms_kernels.hip: the optional terms attached by lemo_prox_set_terms
+int prox_terms_check(const lemo_prox_desc& d, const lemo_prox_terms& t);
+bool prox_terms_any(const lemo_prox_terms& t);
+int prox_terms_run(const lemo_prox_desc& d, const lemo_prox_terms& t, hipStream_t s);
 }
 using namespace lemo;
 
@@ -18,12 +22,15 @@ static const int PROX_UNROLL[PROX_LEVELS] = {10, 1};
 
 struct ProxEngine {
   lemo_prox_desc d;
+  lemo_prox_terms terms;          // read only when has_terms
+  bool has_terms = false;
   hipGraphExec_t exec[PROX_LEVELS] = {nullptr, nullptr};
 };
 
 // forward + backward of one iteration (fitting_func :239-311 without the erase, which the update applies)
 // `fused_tail`: h1 (first VPoser layer) is already there and the last layer of the VPoser backward is left to prox_tail
-static int prox_closure(const lemo_prox_desc& d, hipStream_t s, bool fused_tail = false) {
+// `terms`: the optional terms (contact, scan, self-penetration, marker velocity) between prox_sparse and the all-vertex backward
+static int prox_closure(const lemo_prox_desc& d, const lemo_prox_terms* terms, hipStream_t s, bool fused_tail = false) {
   const int B = d.B, nj = d.body.nj;
   const int H = 3 * d.fit.n81 + 2, W = B - 1 + 16;
   // ---- body: VPoser decode (:243), ONE SMPL-X forward for both joint sets (:248, :253-258)
@@ -50,6 +57,7 @@ static int prox_closure(const lemo_prox_desc& d, hipStream_t s, bool fused_tail 
   CHK(enc_chain_bwd(d, H, W, s, &cur, enc_bwd_l_last(d)));
   CHK(enc_bwd_tail(d, cur, H, W, s));
   CHK(prox_sparse(d, cnt, s));
+  if (terms) CHK(prox_terms_run(d, *terms, s));
   CHK(lbs_verts_bwd(d.skin, d.uset, d.pose.A, nj, d.v_posed, d.V, d.dverts, B, d.Bp, d.dvp, d.dA, d.dtr_v, d.dX, s));
   lemo_pose_grad_in gi{d.dA, d.dJtr, d.dX, d.dfp_add};
   lemo_pose_grad_out go{};
@@ -64,21 +72,23 @@ static int prox_closure(const lemo_prox_desc& d, hipStream_t s, bool fused_tail 
 // one optimiser iteration.  Default (round 5): the last VPoser backward layer, Adam and the NEXT iteration's first VPoser layer share
 // one launch (prox_tail; `first`: the run / graph opens with the h1-only form of it) -- 3 launches and 2 kernel boundaries less per
 // iteration; LEMO_PROX_SEPARATE_ADAM: closure + prox_adam as up to round 4 (A/B switch)
-static int prox_iteration(const lemo_prox_desc& d, hipStream_t s, bool first) {
+static int prox_iteration(const ProxEngine* e, hipStream_t s, bool first) {
+  const lemo_prox_desc& d = e->d;
+  const lemo_prox_terms* terms = e->has_terms ? &e->terms : nullptr;
   static const bool separate = getenv("LEMO_PROX_SEPARATE_ADAM") != nullptr;
   if (separate || !d.vposer.w1t) {
-    CHK(prox_closure(d, s));
+    CHK(prox_closure(d, terms, s));
     return prox_adam(d, s);
   }
   if (first) CHK(prox_tail(d, false, s));
-  CHK(prox_closure(d, s, true));
+  CHK(prox_closure(d, terms, s, true));
   return prox_tail(d, true, s);
 }
 
 static int prox_capture(ProxEngine* e, hipStream_t s, int iters, hipGraphExec_t* out) {
   return capture_graph(out, s, true, [&] {
     int rc = 0;
-    for (int i = 0; i < iters && !rc; ++i) rc = prox_iteration(e->d, s, i == 0);
+    for (int i = 0; i < iters && !rc; ++i) rc = prox_iteration(e, s, i == 0);
     return rc;
   });
 }
@@ -106,10 +116,20 @@ void lemo_prox_destroy(void* h) {
   delete e;
 }
 
+int lemo_prox_set_terms(void* h, const lemo_prox_terms* t) {
+  ProxEngine* e = (ProxEngine*)h;
+  if (!e || !t) return LEMO_ERR_ARG;
+  CHK(prox_terms_check(e->d, *t));
+  destroy_graphs(e->exec, PROX_LEVELS);                    // what was captured does not hold the new launches
+  e->terms = *t;
+  e->has_terms = prox_terms_any(*t);
+  return 0;
+}
+
 int lemo_prox_closure(void* h, void* stream) {
   ProxEngine* e = (ProxEngine*)h;
   if (!e) return LEMO_ERR_ARG;
-  return prox_closure(e->d, S(stream));
+  return prox_closure(e->d, e->has_terms ? &e->terms : nullptr, S(stream));
 }
 
 int lemo_prox_step(void* h, int n, int use_graph, void* stream) {
@@ -117,7 +137,7 @@ int lemo_prox_step(void* h, int n, int use_graph, void* stream) {
   if (!e || n < 0) return LEMO_ERR_ARG;
   hipStream_t s = S(stream);
   if (!use_graph) {
-    for (int i = 0; i < n; ++i) CHK(prox_iteration(e->d, s, i == 0));
+    for (int i = 0; i < n; ++i) CHK(prox_iteration(e, s, i == 0));
     return 0;
   }
   // graphs are stream-agnostic once instantiated: kept across stream changes (see fit_graphs)

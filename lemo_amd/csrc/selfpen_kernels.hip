@@ -44,6 +44,7 @@
 //    A zero-area triangle contributes nothing and receives nothing; an empty list gives L = 0 and a zero gradient without a host test.
 // AUTO: see SP_AUTO_MODE below.
 #include "geom_device.hpp"
+#include "fixed_acc.hpp"
 #include "kernels.hpp"
 
 #include <cmath>
@@ -529,8 +530,22 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_loss_fwd_kernel(const float* __re
   if (tid == 0) loss[b] = s_sum[0];
 }
 
+// where the adjoint of a frame is summed: fp32 atomics on gverts (lemo_selfpen_loss_backward: its bits depend on the order of
+// arrival, as they always did) or the 64-bit fixed-point buffer of fixed_acc.hpp (the PROX engine: order-independent)
+struct SpAccF32 {
+  float* gv;
+  __device__ __forceinline__ SpAccF32 frame(size_t off) const { return SpAccF32{gv + off}; }
+  __device__ __forceinline__ void add(size_t i, float v) const { atomicAdd(&gv[i], v); }
+};
+struct SpAccFix {
+  long long* gv; int* flag;
+  __device__ __forceinline__ SpAccFix frame(size_t off) const { return SpAccFix{gv + LEMO_FIX_WORDS * off, flag}; }
+  __device__ __forceinline__ void add(size_t i, float v) const { fix_add(gv, i, v, flag); }
+};
+
 // gradient of gl * sum over the corners of P of Psi_R(corner)^2 with respect to the six vertices, added to gv
-__device__ __forceinline__ void sp_side_bwd(const SpTri& R, const SpTri& P, float sigma, int outside, float gl, float* __restrict__ gv) {
+template <class Acc>
+__device__ __forceinline__ void sp_side_bwd(const SpTri& R, const SpTri& P, float sigma, int outside, float gl, const Acc& gv) {
   typedef SpDual<6> D6;
   D6 q1[3], q2[3], n[3], o[3], r;
 #pragma unroll
@@ -559,7 +574,7 @@ __device__ __forceinline__ void sp_side_bwd(const SpTri& R, const SpTri& P, floa
       Gn[k] += gp * (s.c_h * s.d[k] - s.c_rho * s.h * s.u[k]);
       Go[k] -= gd;
       Gx[k] += gd;
-      atomicAdd(&gv[3 * (size_t)P.id[c] + k], gd);
+      gv.add(3 * (size_t)P.id[c] + k, gd);
     }
     Gr += gp * s.c_r;
   }
@@ -574,16 +589,17 @@ __device__ __forceinline__ void sp_side_bwd(const SpTri& R, const SpTri& P, floa
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
-    atomicAdd(&gv[3 * (size_t)R.id[1] + k], gq[k]);
-    atomicAdd(&gv[3 * (size_t)R.id[2] + k], gq[3 + k]);
-    atomicAdd(&gv[3 * (size_t)R.id[0] + k], -(gq[k] + gq[3 + k]) - Gx[k]);
+    gv.add(3 * (size_t)R.id[1] + k, gq[k]);
+    gv.add(3 * (size_t)R.id[2] + k, gq[3 + k]);
+    gv.add(3 * (size_t)R.id[0] + k, -(gq[k] + gq[3 + k]) - Gx[k]);
   }
 }
 
-// grid (pair block, frame)
+// grid (pair block, frame); gloss NULL: every frame's loss has the gradient gl_all
+template <class Acc>
 __global__ void __launch_bounds__(SP_BLOCK) sp_loss_bwd_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F,
                                                                 const int* __restrict__ pairs, int C, const int* __restrict__ count, float sigma,
-                                                                int outside, const float* __restrict__ gloss, float* __restrict__ gverts) {
+                                                                int outside, const float* __restrict__ gloss, float gl_all, Acc gverts) {
   const int b = blockIdx.y, c = blockIdx.x * SP_BLOCK + threadIdx.x;
   if (c >= sp_listed(count, b, C)) return;
   const float* __restrict__ vf = verts + (size_t)b * V * 3;
@@ -592,8 +608,8 @@ __global__ void __launch_bounds__(SP_BLOCK) sp_loss_bwd_kernel(const float* __re
   sp_tri(vf, V, faces, F, pb[2 * (size_t)c], A);
   sp_tri(vf, V, faces, F, pb[2 * (size_t)c + 1], Bt);
   if (!A.ok || !Bt.ok) return;
-  const float gl = gloss[b];
-  float* __restrict__ gv = gverts + (size_t)b * V * 3;
+  const float gl = gloss ? gloss[b] : gl_all;
+  const Acc gv = gverts.frame((size_t)b * V * 3);
   sp_side_bwd(A, Bt, sigma, outside, gl, gv);
   sp_side_bwd(Bt, A, sigma, outside, gl, gv);
 }
@@ -673,8 +689,19 @@ int selfpen_loss_backward(const float* verts, int B, int V, const int* faces, in
   if (int e = sp_loss_args(verts, B, V, faces, F, pairs, C, sigma)) return e;
   if (!gloss || !gverts) return LEMO_ERR_ARG;
   if (hipError_t e = hipMemsetAsync(gverts, 0, (size_t)B * V * 3 * sizeof(float), s)) return (int)e;
-  hipLaunchKernelGGL(sp_loss_bwd_kernel, dim3((C + SP_BLOCK - 1) / SP_BLOCK, B), dim3(SP_BLOCK), 0, s, verts, V, faces, F, pairs, C, count, sigma,
-                     penalize_outside ? 1 : 0, gloss, gverts);
+  hipLaunchKernelGGL(sp_loss_bwd_kernel<SpAccF32>, dim3((C + SP_BLOCK - 1) / SP_BLOCK, B), dim3(SP_BLOCK), 0, s, verts, V, faces, F, pairs, C, count,
+                     sigma, penalize_outside ? 1 : 0, gloss, 0.f, SpAccF32{gverts});
+  return (int)hipGetLastError();
+}
+
+// the PROX engine's form: gl * dL[b] / dverts of every frame ADDED to the fixed-point buffer acc [B][V][3] (fixed_acc.hpp; the caller
+// zeroes and converts it; two words per entry), so that the sum does not depend on the order of arrival
+int selfpen_loss_backward_fixed(const float* verts, int B, int V, const int* faces, int F, const int* pairs, int C, const int* count, float sigma,
+                                int penalize_outside, float gl, long long* acc, int* flag, hipStream_t s) {
+  if (int e = sp_loss_args(verts, B, V, faces, F, pairs, C, sigma)) return e;
+  if (!acc || !flag) return LEMO_ERR_ARG;
+  hipLaunchKernelGGL(sp_loss_bwd_kernel<SpAccFix>, dim3((C + SP_BLOCK - 1) / SP_BLOCK, B), dim3(SP_BLOCK), 0, s, verts, V, faces, F, pairs, C, count,
+                     sigma, penalize_outside ? 1 : 0, (const float*)nullptr, gl, SpAccFix{acc, flag});
   return (int)hipGetLastError();
 }
 

@@ -81,6 +81,67 @@ def _masked_mean(x: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     return (x * m).sum() / m.sum().clamp(min=1.0)
 
 
+def optional_terms(body_model: SMPLX, dev, B: int, scene_v, contact_verts_ids, scan, scan_point_num, body_mask, faces_segm, faces_parents,
+                   ign_part_pairs, selfpen):
+    """The optional-term arguments of :class:`ProxTemporalFitter` and :class:`ProxWindowEngine`, checked and put on the device once
+    (one set of checks and messages for both) -> a namespace: ``scene_v`` [1, M, 3], ``contact_ids`` int64, ``scan``,
+    ``scan_point_num``, ``body_mask``, ``faces`` (None without a scan), ``sp_cfg`` (sigma, penalize_outside, max_pairs) and
+    ``sp_tables`` = (faces, segm, parents, ign) or None off the device."""
+    from types import SimpleNamespace
+    o = SimpleNamespace()
+    # body-scene contact (fitting_temp_slide.py:743-753, `contact: True`): scene vertices [M, 3] / [1, M, 3] on the device and the
+    # caller's contact vertex ids; active only with both and a positive weights['contact_loss_weight'] (default 0)
+    o.scene_v = o.contact_ids = None
+    if scene_v is not None and contact_verts_ids is not None:
+        from .chamfer import contact_ids_tensor
+        if not isinstance(scene_v, torch.Tensor) or scene_v.device != dev or scene_v.dtype != torch.float32 or scene_v.shape[-1] != 3 \
+                or scene_v.dim() not in (2, 3) or (scene_v.dim() == 3 and scene_v.shape[0] != 1) or scene_v.numel() < 3:
+            raise ValueError('scene_v must be a float32 [M, 3] or [1, M, 3] tensor on the device of the SDF')
+        o.scene_v = scene_v.detach().reshape(1, -1, 3).contiguous()
+        o.contact_ids = contact_ids_tensor(contact_verts_ids, int(body_model.data.V), dev)
+    # scan-to-mesh / mesh-to-scan (fitting_temp_slide.py:637-670, `s2m: True` / `m2s: True`): the padded scan [B, S, 3] in camera
+    # coordinates, its valid counts [B] and the body mask [V], all on the device; active only with all three and a positive
+    # weights['s2m_weight'] / weights['m2s_weight'] (default 0).  The counts are checked here, once.
+    o.scan = o.scan_point_num = o.body_mask = o.faces = None
+    if scan is not None and scan_point_num is not None and body_mask is not None:
+        V = int(body_model.data.V)
+        if not isinstance(scan, torch.Tensor) or scan.device != dev or scan.dtype != torch.float32 or scan.dim() != 3 or \
+                scan.shape[0] != B or scan.shape[1] < 1 or scan.shape[2] != 3:
+            raise ValueError(f'scan must be a float32 [B = {B}, S, 3] tensor on the device of the SDF')
+        if not isinstance(scan_point_num, torch.Tensor) or scan_point_num.device != dev or scan_point_num.dtype != torch.int32 or \
+                tuple(scan_point_num.shape) != (B,):
+            raise ValueError(f'scan_point_num must be an int32 [{B}] tensor on the device of the SDF')
+        if int(scan_point_num.min()) < 0 or int(scan_point_num.max()) > scan.shape[1]:
+            raise ValueError(f'scan_point_num must lie in 0 .. S = {scan.shape[1]}')
+        if not isinstance(body_mask, torch.Tensor) or body_mask.device != dev or body_mask.dtype != torch.bool or \
+                tuple(body_mask.shape) != (V,):
+            raise ValueError(f'body_mask must be a bool [{V}] tensor on the device of the SDF')
+        o.scan, o.scan_point_num, o.body_mask = scan.detach().contiguous(), scan_point_num.contiguous(), body_mask.contiguous()
+        o.faces = torch.from_numpy(np.ascontiguousarray(body_model.faces, np.int32)).to(dev)     # uploaded once
+    # self-penetration (fitting_temp_slide.py:618-635, `interpenetration: True`): the part segmentation of the faces (optional, as
+    # FilterFaces takes it) and `selfpen` = dict(sigma, penalize_outside, max_pairs); active only with a positive
+    # weights['coll_loss_weight'] (default 0).  The tables are uploaded here, once.
+    sp = dict(selfpen or {})
+    unknown = set(sp) - {'sigma', 'penalize_outside', 'max_pairs'}
+    if unknown:
+        raise ValueError(f'selfpen: unknown keys {sorted(unknown)} (sigma, penalize_outside, max_pairs)')
+    from . import selfpen as _sp
+    o.sp_cfg = dict(sigma=_sp._sigma(sp.get('sigma', 1e-4)), penalize_outside=bool(sp.get('penalize_outside', True)),
+                    max_pairs=int(sp.get('max_pairs', _sp.DEFAULT_MAX_PAIRS)))
+    if o.sp_cfg['max_pairs'] < 1:
+        raise ValueError('selfpen: max_pairs must be at least 1')
+    if (faces_parents is not None or ign_part_pairs is not None) and faces_segm is None:
+        raise ValueError('faces_parents / ign_part_pairs need faces_segm')
+    lib_ = body_model._lib_override or (_hip.get_lib() if dev.type == 'cuda' else None)
+    o.sp_tables = None
+    if lib_ is not None:
+        nF = int(np.asarray(body_model.faces).shape[0])
+        o.sp_tables = (torch.from_numpy(np.ascontiguousarray(body_model.faces, np.int32)).to(dev),
+                       _sp._per_face(lib_, faces_segm, nF, dev, 'faces_segm'), _sp._per_face(lib_, faces_parents, nF, dev, 'faces_parents'),
+                       _sp._ign(lib_, ign_part_pairs, dev)[0])
+    return o
+
+
 class ProxTemporalFitter:
     """One sliding window (B frames) of the PROX temporal fit."""
 
@@ -119,56 +180,13 @@ class ProxTemporalFitter:
         self.body_markers_rec = None if body_markers_rec is None else f(body_markers_rec)
         self.contact_lbl_rec = None if contact_lbl_rec is None else f(contact_lbl_rec)
         self.first_batch_flag = first_batch_flag
-        # body-scene contact (fitting_temp_slide.py:743-753, `contact: True`): scene vertices [M, 3] / [1, M, 3] on the device and the
-        # caller's contact vertex ids; active only with both and a positive weights['contact_loss_weight'] (default 0)
-        self.scene_v = self.contact_ids = None
-        if scene_v is not None and contact_verts_ids is not None:
-            from .chamfer import contact_ids_tensor
-            if not isinstance(scene_v, torch.Tensor) or scene_v.device != dev or scene_v.dtype != torch.float32 or scene_v.shape[-1] != 3 \
-                    or scene_v.dim() not in (2, 3) or (scene_v.dim() == 3 and scene_v.shape[0] != 1) or scene_v.numel() < 3:
-                raise ValueError('scene_v must be a float32 [M, 3] or [1, M, 3] tensor on the device of the SDF')
-            self.scene_v = scene_v.detach().reshape(1, -1, 3).contiguous()
-            self.contact_ids = contact_ids_tensor(contact_verts_ids, int(self.body_model.data.V), dev)
-        # scan-to-mesh / mesh-to-scan (fitting_temp_slide.py:637-670, `s2m: True` / `m2s: True`): the padded scan [B, S, 3] in camera
-        # coordinates, its valid counts [B] and the body mask [V], all on the device; active only with all three and a positive
-        # weights['s2m_weight'] / weights['m2s_weight'] (default 0).  The counts are checked here, once.
-        self.scan = self.scan_point_num = self.body_mask = None
-        if scan is not None and scan_point_num is not None and body_mask is not None:
-            V = int(self.body_model.data.V)
-            if not isinstance(scan, torch.Tensor) or scan.device != dev or scan.dtype != torch.float32 or scan.dim() != 3 or \
-                    scan.shape[0] != B or scan.shape[1] < 1 or scan.shape[2] != 3:
-                raise ValueError(f'scan must be a float32 [B = {B}, S, 3] tensor on the device of the SDF')
-            if not isinstance(scan_point_num, torch.Tensor) or scan_point_num.device != dev or scan_point_num.dtype != torch.int32 or \
-                    tuple(scan_point_num.shape) != (B,):
-                raise ValueError(f'scan_point_num must be an int32 [{B}] tensor on the device of the SDF')
-            if int(scan_point_num.min()) < 0 or int(scan_point_num.max()) > scan.shape[1]:
-                raise ValueError(f'scan_point_num must lie in 0 .. S = {scan.shape[1]}')
-            if not isinstance(body_mask, torch.Tensor) or body_mask.device != dev or body_mask.dtype != torch.bool or \
-                    tuple(body_mask.shape) != (V,):
-                raise ValueError(f'body_mask must be a bool [{V}] tensor on the device of the SDF')
-            self.scan, self.scan_point_num, self.body_mask = scan.detach().contiguous(), scan_point_num.contiguous(), body_mask.contiguous()
-            self._scan_faces = torch.from_numpy(np.ascontiguousarray(self.body_model.faces, np.int32)).to(dev)     # uploaded once
-        # self-penetration (fitting_temp_slide.py:618-635, `interpenetration: True`): the part segmentation of the faces (optional, as
-        # FilterFaces takes it) and `selfpen` = dict(sigma, penalize_outside, max_pairs); active only with a positive
-        # weights['coll_loss_weight'] (default 0).  The tables are uploaded here, once.
-        sp = dict(selfpen or {})
-        unknown = set(sp) - {'sigma', 'penalize_outside', 'max_pairs'}
-        if unknown:
-            raise ValueError(f'selfpen: unknown keys {sorted(unknown)} (sigma, penalize_outside, max_pairs)')
-        from . import selfpen as _sp
-        self._sp_cfg = dict(sigma=_sp._sigma(sp.get('sigma', 1e-4)), penalize_outside=bool(sp.get('penalize_outside', True)),
-                            max_pairs=int(sp.get('max_pairs', _sp.DEFAULT_MAX_PAIRS)))
-        if self._sp_cfg['max_pairs'] < 1:
-            raise ValueError('selfpen: max_pairs must be at least 1')
-        if (faces_parents is not None or ign_part_pairs is not None) and faces_segm is None:
-            raise ValueError('faces_parents / ign_part_pairs need faces_segm')
-        lib_ = self.body_model._lib_override or (_hip.get_lib() if dev.type == 'cuda' else None)
-        self._sp_tables = None
-        if lib_ is not None:
-            nF = int(np.asarray(self.body_model.faces).shape[0])
-            self._sp_tables = (torch.from_numpy(np.ascontiguousarray(self.body_model.faces, np.int32)).to(dev),
-                               _sp._per_face(lib_, faces_segm, nF, dev, 'faces_segm'), _sp._per_face(lib_, faces_parents, nF, dev, 'faces_parents'),
-                               _sp._ign(lib_, ign_part_pairs, dev)[0])
+        ot = optional_terms(self.body_model, dev, B, scene_v, contact_verts_ids, scan, scan_point_num, body_mask, faces_segm, faces_parents,
+                            ign_part_pairs, selfpen)
+        self.scene_v, self.contact_ids = ot.scene_v, ot.contact_ids
+        self.scan, self.scan_point_num, self.body_mask = ot.scan, ot.scan_point_num, ot.body_mask
+        if ot.scan is not None:
+            self._scan_faces = ot.faces
+        self._sp_cfg, self._sp_tables = ot.sp_cfg, ot.sp_tables
         self.params = [p for n, p in self.body_model.named_parameters() if p.requires_grad] + [self.pose_embedding]
         # optim_factory.py:43-46.  capturable: the step count lives on the device so that a captured step can be replayed
         self.optimizer = torch.optim.Adam(self.params, lr=lr, capturable=self.pose_embedding.is_cuda)
@@ -382,14 +400,22 @@ class ProxWindowEngine(NativeEngine):
     ``fitting_func`` (fitting_temp_slide.py:239-311), the S2 / S3-active ``SMPLifyLoss`` terms, backward, first-15 % erase
     and Adam (lr 0.005) are a fixed sequence of ~40 HIP kernels captured once and replayed -- no torch op, no host sync,
     no atomics-ordered accumulation (graph replay == eager launches bit for bit).  Same constructor as
-    :class:`ProxTemporalFitter` (which stays as the module-level / autograd composition of the same kernels)."""
+    :class:`ProxTemporalFitter` (which stays as the module-level / autograd composition of the same kernels), the optional
+    terms included: ``scene_v`` / ``contact_verts_ids``, ``scan`` / ``scan_point_num`` / ``body_mask``, ``faces_segm`` /
+    ``faces_parents`` / ``ign_part_pairs`` / ``selfpen`` with the ``weights[...]`` keys ``contact_loss_weight``, ``s2m_weight``,
+    ``m2s_weight``, ``rho_s2m``, ``rho_m2s``, ``coll_loss_weight``, ``smooth_acc_weight``, ``smooth_vel_weight`` (default 0 / rho 1)
+    run inside the captured iteration (``lemo_prox_set_terms``, csrc/prox_terms_kernels.hip); their scattered gradients are summed
+    in fixed point with integer atomics, so the bit-for-bit contract holds with them.  A non-finite scan point latches ``nonfinite_step()``."""
     _destroy = 'prox_destroy'
 
     def __init__(self, body_model: SMPLX, vposer: VPoser, smooth_encoder: Enc, ids: Dict[str, np.ndarray], Xmean, Xstd,
                  weights: dict, R, t, sdf: torch.Tensor, grid_min, grid_max, params: Dict[str, np.ndarray], gt_joints,
                  joints_conf, joint_map=None, fric_ids=None, cam: Optional[dict] = None, marker_mask=None,
                  body_markers_rec=None, contact_lbl_rec=None, first_batch_flag: bool = False, lr: float = 0.005,
-                 conv_variant: Optional[int] = None):
+                 conv_variant: Optional[int] = None, scene_v: Optional[torch.Tensor] = None, contact_verts_ids=None,
+                 scan: Optional[torch.Tensor] = None, scan_point_num: Optional[torch.Tensor] = None,
+                 body_mask: Optional[torch.Tensor] = None, faces_segm=None, faces_parents=None, ign_part_pairs=None,
+                 selfpen: Optional[dict] = None):
         import ctypes as C
         from ._hip import ptr
         from .body_model import K_PAD, alloc_pose_ws
@@ -530,8 +556,87 @@ class ProxWindowEngine(NativeEngine):
         if not self.handle:
             raise _hip.LemoHipError('lemo_prox_create rejected the descriptor')
         self.first_batch_flag = bool(first_batch_flag)
+        # the optional terms (contact, s2m / m2s, self-penetration, marker acceleration / velocity): the fitter's arguments, checks and
+        # weights[...] keys; attached only when one of them is live -- otherwise the new entry is not called and the launches stay as
+        # they were
+        self._attach_terms(optional_terms(body_model, dev, B, scene_v, contact_verts_ids, scan, scan_point_num, body_mask, faces_segm,
+                                          faces_parents, ign_part_pairs, selfpen))
         self._init_order(self.device, lib)
         self._after_write()          # the parameter copies above were enqueued on the constructor's current stream
+
+    def _attach_terms(self, ot) -> None:
+        """scratch for the live optional terms (sizes from the searches' own ``lemo_*_workspace_bytes``) + ``lemo_prox_set_terms``"""
+        import ctypes as C
+        from ._hip import ptr
+        lib, dev, B, V, w = self.lib, self.device, self.B, int(self.data.V), self.w
+        weight = lambda k: float(w.get(k, 0))
+        contact = ot.scene_v is not None and weight('contact_loss_weight') > 0
+        s2m = ot.scan is not None and weight('s2m_weight') > 0
+        m2s = ot.scan is not None and weight('m2s_weight') > 0
+        pen = weight('coll_loss_weight') > 0
+        acc, vel = weight('smooth_acc_weight') > 0, weight('smooth_vel_weight') > 0
+        self.terms = self._terms_t = None
+        if not (contact or s2m or m2s or pen or acc or vel):
+            return
+        e = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+
+        def scratch(nbytes, what):
+            if nbytes < 0:
+                raise _hip.LemoHipError(f'ProxWindowEngine: the {what} does not take these shapes')
+            return e(max(int(nbytes), 8), torch.uint8), int(nbytes)
+        T_ = self._terms_t = {}
+        t = _hip.ProxTerms()
+        if contact:
+            ids = ot.contact_ids.cpu().numpy().astype(np.int32)
+            if len(np.unique(ids)) != ids.size:                  # each id owns one gradient row: that is what makes the adjoint atomic-free
+                raise ValueError('contact_verts_ids must be unique for ProxWindowEngine')
+            M, Nc = int(ot.scene_v.shape[1]), int(ids.size)
+            T_['scene_v'], T_['cvid'], T_['cvid_host'] = ot.scene_v, torch.from_numpy(ids).to(dev), np.ascontiguousarray(ids)
+            T_['cxyz'], T_['cdist'], T_['cidx'] = e((B, Nc, 3), torch.float32), e((B, Nc), torch.float32), e((B, Nc), torch.int32)
+            T_['cws'], t.contact_ws_bytes = scratch(lib.chamfer_workspace_bytes(B, Nc, M, 1, 0), 'contact search')
+            t.scene_v, t.M, t.contact_vid, t.contact_vid_host, t.Nc = ptr(T_['scene_v']), M, ptr(T_['cvid']), T_['cvid_host'].ctypes.data, Nc
+            t.contact_loss_weight = weight('contact_loss_weight')
+            t.contact_xyz, t.contact_dist, t.contact_idx, t.contact_ws = ptr(T_['cxyz']), ptr(T_['cdist']), ptr(T_['cidx']), ptr(T_['cws'])
+        if s2m or m2s or pen:
+            T_['faces'] = ot.faces if ot.faces is not None else ot.sp_tables[0]
+            t.faces, t.F = ptr(T_['faces']), int(T_['faces'].shape[0])
+        if s2m or m2s:
+            S = int(ot.scan.shape[1])
+            T_['scan'], T_['spn'], T_['body_mask'] = ot.scan, ot.scan_point_num, ot.body_mask.view(torch.uint8)
+            T_['vis'], T_['qmask'], T_['counts'] = e((B, V), torch.uint8), e((B, V), torch.uint8), torch.zeros(3, B, dtype=torch.int32, device=dev)
+            T_['s2m_dist'], T_['s2m_idx'] = e((B, S), torch.float32), e((B, S), torch.int32)
+            T_['m2s_dist'], T_['m2s_idx'] = e((B, V), torch.float32), e((B, V), torch.int32)
+            T_['vis_ws'], t.vis_ws_bytes = scratch(lib.vertex_visibility_workspace_bytes(B, V, t.F, 0, 0), 'visibility')
+            T_['scan_ws'], t.scan_ws_bytes = scratch(max(lib.chamfer_workspace_bytes(B, S, V, 0, 0), lib.chamfer_workspace_bytes(B, V, S, 0, 0))
+                                                     if min(lib.chamfer_workspace_bytes(B, S, V, 0, 0), lib.chamfer_workspace_bytes(B, V, S, 0, 0)) >= 0
+                                                     else -1, 'scan search')
+            t.scan, t.S, t.scan_point_num, t.body_mask = ptr(T_['scan']), S, ptr(T_['spn']), ptr(T_['body_mask'])
+            t.s2m_weight, t.m2s_weight = weight('s2m_weight'), weight('m2s_weight')
+            t.rho_s2m, t.rho_m2s, t.min_dist = float(w.get('rho_s2m', 1)), float(w.get('rho_m2s', 1)), 1e-3
+            t.vis, t.qmask, t.scan_counts = ptr(T_['vis']), ptr(T_['qmask']), ptr(T_['counts'])
+            t.s2m_dist, t.s2m_idx, t.m2s_dist, t.m2s_idx = ptr(T_['s2m_dist']), ptr(T_['s2m_idx']), ptr(T_['m2s_dist']), ptr(T_['m2s_idx'])
+            t.vis_ws, t.scan_ws = ptr(T_['vis_ws']), ptr(T_['scan_ws'])
+        if pen:
+            if ot.sp_tables is None:
+                raise _hip.LemoHipError('the self-penetration term needs tensors on a HIP device (no CPU fallback)')
+            _, segm, par, ign = ot.sp_tables
+            Cp = int(ot.sp_cfg['max_pairs'])
+            T_['segm'], T_['par'], T_['ign'] = segm, par, ign
+            T_['pairs'], T_['pair_count'], T_['pen_loss'] = e((B, Cp, 2), torch.int32), torch.zeros(B, dtype=torch.int32, device=dev), e(B, torch.float32)
+            T_['pen_ws'], t.pen_ws_bytes = scratch(lib.selfpen_search_workspace_bytes(B, V, t.F, 0, 0), 'collision search')
+            t.segm, t.parents, t.ign, t.P = ptr(segm), ptr(par), ptr(ign), 0 if ign is None else int(ign.shape[0])
+            t.coll_loss_weight, t.sigma = weight('coll_loss_weight'), float(ot.sp_cfg['sigma'])
+            t.penalize_outside, t.max_pairs = int(ot.sp_cfg['penalize_outside']), Cp
+            t.pairs, t.pair_count, t.pen_loss, t.pen_ws = ptr(T_['pairs']), ptr(T_['pair_count']), ptr(T_['pen_loss']), ptr(T_['pen_ws'])
+        t.smooth_acc_weight, t.smooth_vel_weight = weight('smooth_acc_weight'), weight('smooth_vel_weight')
+        if s2m or pen:
+            T_['fix_acc'] = torch.zeros(B, V, 3, 2, dtype=torch.int64, device=dev)        # csrc/fixed_acc.hpp: two words per entry
+            t.fix_acc = ptr(T_['fix_acc'])
+        T_['fix_flag'] = torch.zeros(1, dtype=torch.int32, device=dev)
+        T_['frame_acc'] = torch.zeros(B, 8, dtype=torch.float64, device=dev)
+        t.fix_flag, t.frame_acc = ptr(T_['fix_flag']), ptr(T_['frame_acc'])
+        self.terms = t
+        lib.check(lib.prox_set_terms(self.handle, C.byref(t)), 'prox_set_terms')
 
     def closure(self) -> Dict[str, float]:
         """forward + backward (no update, no erase): fills the loss record and the gradient buffers"""
