@@ -896,6 +896,47 @@ int lemo_occlusion_query(const float* verts, int T, int V, const int* faces, int
                          float proj_fx, float proj_fy, const float* depth_scene, float thresh, unsigned* ws, float* mask,
                          float* depth_body, int* pix, void* stream);
 
+/* ---- body overlays (csrc/render_kernels.hip): the render_results branch of temp_prox/fit_temp_loadprox_slide.py:622-683 ----
+ * The camera, the coverage and the depth are lemo_depth_raster's (same device functions: the depth of a frame is bit for bit what
+ * lemo_depth_raster writes for that frame's mesh).  Everything is deterministic: no float atomics, the same bits whatever the order
+ * of faces, the number of frames per call or the run.  All memory is the caller's; nothing synchronises.
+ * LEMO_ERR_SHAPE: B, V, F, P < 1, B > 65535, F > 2^30, B V > 2^30, W or H outside [1, 32768], radius outside [0, 16], nnz < 0;
+ * LEMO_ERR_ARG: null pointers, a camera lemo_depth_raster refuses, shading values outside [0, 1] or not finite, an unknown background
+ * kind, a colour above 0xFFFFFF.  Nothing is launched then.
+ *
+ * lemo_vertex_normals: verts [B][V][3], faces [F][3]; adj_start [V + 1], adj_face [nnz]: for vertex v the faces
+ *   adj_face[adj_start[v] .. adj_start[v + 1]) that contain it, in ascending order, each once (the CALLER's to build and to keep
+ *   inside [0, F); entries outside it are skipped, as are faces that name a vertex outside [0, V)).  sums [B][V][3] (or NULL): the sum
+ *   of (p1 - p0) x (p2 - p0) over those faces in that order; normals [B][V][3] (or NULL): sums / sqrt(sums . sums), (0, 0, 0) where
+ *   sums . sums is not > 0.  At least one of the two outputs.
+ * lemo_render_ids: verts [B][V][3] in camera space -> keys [B][H][W] (the raster's depth keys, scratch), ids [B][H][W]:
+ *   0xFFFFFFFF - f of the lowest-index face f among those whose depth at the pixel is the nearest, 0 where nothing is hit; depth
+ *   [B][H][W] (or NULL): camera-space Z, 0 where nothing is hit.
+ * lemo_render_resolve: rgb [B][H][W][3] uint8 <- per covered pixel the quantised colour base_k * shade,
+ *   shade = min(1, ambient + diffuse |n_z| / |n|) with n the perspective-correct interpolation of the three vertex normals [B][V][3]
+ *   (weights e_i / (e0 + e1 + e2) of the face's edge functions at the pixel's ray; 0 instead of |n_z| / |n| where |n| = 0),
+ *   q = (int)(255 c + 0.5) clamped to 0 .. 255; per uncovered pixel the background's pixel -- background [B][H][W][3], or [H][W][3]
+ *   with bg_shared, of uint8 (LEMO_RENDER_BG_U8) or of float32 in [0, 1] quantised by the same rule (LEMO_RENDER_BG_F32; a NaN gives
+ *   0) -- or (0, 0, 0) with LEMO_RENDER_BG_NONE.  Optional (or NULL): face_ids [B][H][W] int32, -1 where nothing is hit; shade
+ *   [B][H][W], 0 where nothing is hit.  ids as lemo_render_ids wrote them for the same verts, faces and cam.
+ * lemo_render_points: points [B][P][2] pixel coordinates (u, v); x = trunc(u), y = trunc(v); every pixel (x + i, y + j) with
+ *   i^2 + j^2 <= radius^2 inside the image gets color (0xRRGGBB).  Points that are not finite (or do not fit an int) are skipped. */
+typedef struct lemo_render_shade {
+  float base[3];                  /* base colour, each in [0, 1] */
+  float ambient, diffuse;         /* each in [0, 1] */
+} lemo_render_shade;
+#define LEMO_RENDER_BG_NONE 0
+#define LEMO_RENDER_BG_U8 1
+#define LEMO_RENDER_BG_F32 2
+int lemo_vertex_normals(const float* verts, int B, int V, const int* faces, int F, const int* adj_start, const int* adj_face, int nnz,
+                        float* normals, float* sums, void* stream);
+int lemo_render_ids(const float* verts, int B, int V, const int* faces, int F, const lemo_occl_cam* cam, unsigned* keys, unsigned* ids,
+                    float* depth, void* stream);
+int lemo_render_resolve(const float* verts, const float* normals, int B, int V, const int* faces, int F, const lemo_occl_cam* cam,
+                        const unsigned* ids, const lemo_render_shade* shade_par, const void* background, int bg_kind, int bg_shared,
+                        unsigned char* rgb, int* face_ids, float* shade, void* stream);
+int lemo_render_points(const float* points, int B, int P, int radius, int W, int H, unsigned color, unsigned char* rgb, void* stream);
+
 /* ---- Chamfer nearest neighbours (csrc/chamfer_kernels.hip): the `chamfer` extension of temp_prox/dist_chamfer.py:27,43 and the
  * scene-contact term of fitting_temp_slide.py:743-753 ----
  * xyz1 [B][N][3], xyz2 [B][M][3] (or [1][M][3] with LEMO_CHAMFER_SHARED: one target set for every batch entry, never copied); fp32,

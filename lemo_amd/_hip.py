@@ -109,6 +109,11 @@ class OcclCam(C.Structure):
                 ('W', C.c_int), ('H', C.c_int), ('cull_backface', C.c_int)]
 
 
+class RenderShade(C.Structure):
+    """lemo_render_shade"""
+    _fields_ = [('base', C.c_float * 3), ('ambient', C.c_float), ('diffuse', C.c_float)]
+
+
 class DepthCalib(C.Structure):
     """lemo_depth_calib"""
     _fields_ = [('rays', vp), ('view_d', C.c_float * 12), ('Rc', C.c_float * 9), ('Tc', C.c_float * 3), ('fx', C.c_float), ('fy', C.c_float),
@@ -367,6 +372,11 @@ _SIGS = {
     'lemo_depth_raster': (C.c_int, [vp, C.c_int, vp, C.c_int, C.POINTER(C.c_float), C.POINTER(OcclCam), vp, vp]),
     'lemo_occlusion_query': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.POINTER(OcclCam), C.c_float, C.c_float, vp, C.c_float,
                                        vp, vp, vp, vp, vp]),
+    'lemo_vertex_normals': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
+    'lemo_render_ids': (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(OcclCam), vp, vp, vp, vp]),
+    'lemo_render_resolve': (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(OcclCam), vp, C.POINTER(RenderShade), vp, C.c_int, C.c_int,
+                                      vp, vp, vp, vp]),
+    'lemo_render_points': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, vp, vp]),
     'lemo_chamfer_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'lemo_chamfer_forward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong, vp]),
     'lemo_chamfer_backward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
