@@ -114,7 +114,9 @@ int lemo_conv3x3_wino_f16(const float* in, const void* wU, float winv, const flo
 int lemo_conv3x3_c1(const float* x0, const float* w, const float* bias, float* out, int H, int W, int cout, void* stream);
 int lemo_conv3x3_c1_bwd(const float* dpre, const float* w, float* dx0, int H, int W, int cout, void* stream);
 /* loss_smooth = mean((z[...,1:]-z[...,:-1])^2)  (opt_amass_temp.py:390-391) fused with d(loss)/d(pre-act):
- * partial[lemo_smooth_loss_blocks()] receives per-block sums of squares; coef2 = weight*2/count */
+ * partial[lemo_smooth_loss_blocks()] receives per-block sums of squares; coef2 = weight*2/count.  z, dpre: CG8P; the border
+ * of z is loaded but never used, the border of dpre is not written.  LEMO_ERR_SHAPE for H < 1, W < 1, C < 8 or C % 8,
+ * LEMO_ERR_ARG for a null z or dpre */
 int lemo_smooth_loss_blocks(int H, int W, int C);
 int lemo_smooth_loss(const float* z, float* dpre, float* partial, int H, int W, int C, float coef2, void* stream);
 

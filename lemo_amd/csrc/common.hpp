@@ -133,7 +133,7 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 }
 
 // ---- torch.optim.Adam (defaults), one element, OPERATION FOR OPERATION as torch's CPU kernels evaluate it -- probed bit for bit
-// against torch 2.10 (tests/test_adam_bits.py; rounds 1-3 used (1.f - 0.999f) for 1 - beta2, 1.3e-5 away from torch's 0.001f):
+// against torch 2.10 (tests/small_kernels_common.py; rounds 1-3 used (1.f - 0.999f) for 1 - beta2, 1.3e-5 away from torch's 0.001f):
 //   exp_avg.lerp_(g, 1 - b1)                        m' = fma(g - m, 0.1f, m)
 //   exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)      v' = fma(0.001f * g, g, v * 0.999f)
 //   denom = sqrt(v') / sqrt(1 - b2^t) + eps         (the bias correction's square root in double, rounded once)

@@ -661,7 +661,7 @@ smooth_loss_kernel(const float* __restrict__ z, float* __restrict__ dpre, float*
 int smooth_loss_blocks(int H, int W, int C) { return (H * W * (C / 8) * 2 + 256 * LEMO_SMOOTH_ITEMS - 1) / (256 * LEMO_SMOOTH_ITEMS); }
 
 int smooth_loss(const float* z, float* dpre, float* partial, int H, int W, int C, float coef2, hipStream_t s, double* acc) {
-  if (C % 8 || (!partial && !acc)) return LEMO_ERR_SHAPE;
+  if (H < 1 || W < 1 || C < 8 || C % 8 || (!partial && !acc)) return LEMO_ERR_SHAPE;
   hipLaunchKernelGGL(smooth_loss_kernel, dim3(smooth_loss_blocks(H, W, C)), dim3(256), 0, s, z, dpre, partial, H, W, C, coef2, acc);
   return (int)hipGetLastError();
 }

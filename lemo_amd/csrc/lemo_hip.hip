@@ -124,6 +124,7 @@ int lemo_conv3x3_c1_bwd(const float* dpre, const float* w, float* dx0, int H, in
 }
 int lemo_smooth_loss_blocks(int H, int W, int C) { return smooth_loss_blocks(H, W, C); }
 int lemo_smooth_loss(const float* z, float* dpre, float* partial, int H, int W, int C, float coef2, void* stream) {
+  if (!z || !dpre) return LEMO_ERR_ARG;
   return smooth_loss(z, dpre, partial, H, W, C, coef2, S(stream));
 }
 
