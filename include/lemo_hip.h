@@ -939,6 +939,36 @@ int lemo_render_resolve(const float* verts, const float* normals, int B, int V, 
                         unsigned char* rgb, int* face_ids, float* shade, void* stream);
 int lemo_render_points(const float* points, int B, int P, int radius, int W, int H, unsigned color, unsigned char* rgb, void* stream);
 
+/* ---- 3-D views of fitted bodies (csrc/view_kernels.hip): temp_prox/renderer.py '3d' mode, temp_prox/viz/viz_fitting.py,
+ * vis_opt_amass.py -- the body inside the coloured scene mesh, markers as spheres.  The rules are written out in
+ * lemo_amd/scene_view.py.  Deterministic, no atomics of their own; all memory is the caller's; nothing synchronises.
+ * LEMO_ERR_SHAPE: n, B, V, F < 1, n > 2^30, B > 65535, F > 2^30, B V > 2^30, P outside [0, 256], W or H outside [1, 32768];
+ * LEMO_ERR_ARG: null pointers, a camera lemo_depth_raster refuses, a transform that is not finite, shading values outside [0, 1], a
+ * colour above 0xFFFFFF, a scene key without scene rgb or the reverse.  Nothing is launched then.
+ *
+ * lemo_view_transform: points [n][3] -> out [n][3], each through xf (host [12], [R | t] row-major) as lemo_depth_raster applies its
+ *   xf on load: ((m0 x + m1 y) + m2 z) + m3 per row.
+ * lemo_view_scene_resolve: the static layer of one view.  verts [V][3] in camera space, normals [V][3] (may be NULL when lit == 0),
+ *   ids [H][W] as lemo_render_ids wrote them for B = 1, colors [V][3] uint8 -> rgb [H][W][3]: per covered pixel
+ *   q(((b0 C0 + b1 C1) + b2 C2) shade), C = uint8 / 255, b_i the weights lemo_render_resolve interpolates normals with,
+ *   shade = lemo_render_resolve's (1 when lit == 0); (0, 0, 0) where nothing is hit.
+ * lemo_view_compose: B frames.  verts, normals [B][V][3] (camera space), keys, ids [B][H][W] as lemo_render_ids wrote them;
+ *   scene_key [H][W] (the keys lemo_render_ids left for the scene) with scene_rgb [H][W][3], or both NULL; spheres [B][P][3] in world
+ *   coordinates (or P = 0), sent through view (host [12], or NULL for the identity), radius [P], sphere_rgb [P][3] (rgb_shared) or
+ *   [B][P][3].  A sphere is hit analytically: A = d . d, q = c x d, disc = A r^2 - q . q >= 0, Z = (d . c - sqrt(disc)) / A inside
+ *   [znear, zfar]; spheres with a centre or radius that is not finite, r <= 0 or c_z - r < znear are not drawn.  Per pixel the
+ *   nearest of the three layers wins (equal depth: body, spheres by lowest index, scene); rgb [B][H][W][3]: the body shaded as
+ *   lemo_render_resolve does, a sphere by its own normal and colour, the scene's rgb, or bg (0xRRGGBB); optional (or NULL) depth
+ *   [B][H][W] (0: nothing) and owner [B][H][W] (-1 nothing, 0 scene, 1 body, 2 + s sphere s). */
+int lemo_view_transform(const float* points, long long n, const float* xf, float* out, void* stream);
+int lemo_view_scene_resolve(const float* verts, const float* normals, int V, const int* faces, int F, const lemo_occl_cam* cam,
+                            const unsigned* ids, const unsigned char* colors, float ambient, float diffuse, int lit, unsigned char* rgb,
+                            void* stream);
+int lemo_view_compose(const float* verts, const float* normals, int B, int V, const int* faces, int F, const lemo_occl_cam* cam,
+                      const unsigned* keys, const unsigned* ids, const lemo_render_shade* shade_par, const unsigned* scene_key,
+                      const unsigned char* scene_rgb, const float* spheres, int P, const float* radius, const unsigned char* sphere_rgb,
+                      int rgb_shared, const float* view, unsigned bg, unsigned char* rgb, float* depth, int* owner, void* stream);
+
 /* ---- Chamfer nearest neighbours (csrc/chamfer_kernels.hip): the `chamfer` extension of temp_prox/dist_chamfer.py:27,43 and the
  * scene-contact term of fitting_temp_slide.py:743-753 ----
  * xyz1 [B][N][3], xyz2 [B][M][3] (or [1][M][3] with LEMO_CHAMFER_SHARED: one target set for every batch entry, never copied); fp32,

@@ -393,6 +393,10 @@ _SIGS = {
     'lemo_render_resolve': (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(OcclCam), vp, C.POINTER(RenderShade), vp, C.c_int, C.c_int,
                                       vp, vp, vp, vp]),
     'lemo_render_points': (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, vp, vp]),
+    'lemo_view_transform': (C.c_int, [vp, C.c_longlong, C.POINTER(C.c_float), vp, vp]),
+    'lemo_view_scene_resolve': (C.c_int, [vp, vp, C.c_int, vp, C.c_int, C.POINTER(OcclCam), vp, vp, C.c_float, C.c_float, C.c_int, vp, vp]),
+    'lemo_view_compose': (C.c_int, [vp, vp, C.c_int, C.c_int, vp, C.c_int, C.POINTER(OcclCam), vp, vp, C.POINTER(RenderShade), vp, vp, vp, C.c_int,
+                                    vp, vp, C.c_int, C.POINTER(C.c_float), C.c_uint, vp, vp, vp, vp]),
     'lemo_chamfer_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'lemo_chamfer_forward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_longlong, vp]),
     'lemo_chamfer_backward': (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),

@@ -1,5 +1,6 @@
-// The raster's device functions, shared by occlusion_kernels.hip (depth raster, per-point query) and render_kernels.hip (batched
-// depth, face ids, shading): ONE oc_setup / oc_key pair, so a depth one of them computes is bit for bit the other's.
+// The raster's device functions, shared by occlusion_kernels.hip (depth raster, per-point query), render_kernels.hip (batched
+// depth, face ids, shading) and view_kernels.hip (scene views): ONE oc_setup / oc_key pair, so a depth one of them computes is bit
+// for bit the other's, and ONE shading function (rn_shade_bary), so a body pixel has the same colour in an overlay and in a view.
 //
 // Geometry.  Camera space is y down, z forward; pixel [y][x] samples the ray d = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1).
 // Coverage uses homogeneous edge functions e_i = d . (p_j x (p_k - p_j)): the ray meets the triangle's plane inside the triangle
@@ -111,6 +112,47 @@ __device__ __forceinline__ bool oc_face(const float* __restrict__ verts, int V, 
 }
 
 __device__ __forceinline__ bool oc_is_big(const OcTri& t) { return (t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1) > OC_BIG; }
+
+// ---- shading, shared by render_kernels.hip (body overlays) and view_kernels.hip (scene views): ONE function, the same bits ------
+struct RnShade { float base[3], ambient, diffuse; };
+
+// (int)(255 c + 0.5) clamped to 0 .. 255 (a NaN gives 0)
+__device__ __forceinline__ unsigned rn_quant(float c) { return (unsigned)(int)fminf(fmaxf(255.0f * c + 0.5f, 0.0f), 255.0f); }
+
+// shade of pixel (x, y) under face f of one frame (rule 3 of lemo_amd/render.py); bw: the perspective-correct weights of the face's
+// three vertices at the pixel's ray (0 for a face that cannot be drawn); lit = false: shade 1, the weights only
+__device__ __forceinline__ float rn_shade_bary(const float* __restrict__ vf, const float* __restrict__ nf, int V, const int* __restrict__ faces,
+                                               int f, const OcCam& c, float ambient, float diffuse, bool lit, int x, int y, float bw[3]) {
+  OcXf X = {};
+  OcTri t;
+  float lam = 0.0f;
+  bw[0] = bw[1] = bw[2] = 0.0f;
+  if (oc_face(vf, V, faces, f, X, c, t)) {                    // true for every id the id pass wrote
+    const float dx = oc_ray_x(x, c), dy = oc_ray_y(y, c);
+    const float e0 = (t.e0[0] * dx + t.e0[1] * dy) + t.e0[2];
+    const float e1 = (t.e1[0] * dx + t.e1[1] * dy) + t.e1[2];
+    const float e2 = (t.e2[0] * dx + t.e2[1] * dy) + t.e2[2];
+    const float s = (e0 + e1) + e2;
+    const float b0 = e0 / s, b1 = e1 / s, b2 = e2 / s;
+    bw[0] = b0; bw[1] = b1; bw[2] = b2;
+    if (!lit) return 1.0f;
+    const float *n0 = nf + 3 * (size_t)faces[3 * (size_t)f], *n1 = nf + 3 * (size_t)faces[3 * (size_t)f + 1],
+                *n2 = nf + 3 * (size_t)faces[3 * (size_t)f + 2];
+    float n[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) n[k] = (b0 * n0[k] + b1 * n1[k]) + b2 * n2[k];
+    const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    if (len > 0.0f) lam = fabsf(n[2]) / len;                  // false also for a NaN
+  }
+  if (!lit) return 1.0f;
+  return fminf(1.0f, ambient + diffuse * lam);
+}
+
+__device__ __forceinline__ float rn_shade(const float* __restrict__ vf, const float* __restrict__ nf, int V, const int* __restrict__ faces, int f,
+                                          const OcCam& c, const RnShade& sh, int x, int y) {
+  float bw[3];
+  return rn_shade_bary(vf, nf, V, faces, f, c, sh.ambient, sh.diffuse, true, x, y, bw);
+}
 
 // the C ABI's camera, validated -> the kernels' (LEMO_ERR_SHAPE / LEMO_ERR_ARG as include/lemo_hip.h documents)
 static inline int oc_cam(const lemo_occl_cam* cam, OcCam& c) {

@@ -23,8 +23,6 @@ namespace lemo {
 
 #define RN_PPT 4                                             // pixels per thread of the resolve: 12 bytes = 3 dwords of uint8 rgb
 
-struct RnShade { float base[3], ambient, diffuse; };
-
 // ---- normals -----------------------------------------------------------------------------------------------------------------
 // grid (vertex blocks, B)
 __global__ void __launch_bounds__(OC_BLOCK) vertex_normals_kernel(const float* __restrict__ verts, int V, const int* __restrict__ faces, int F,
@@ -116,33 +114,7 @@ __global__ void __launch_bounds__(OC_BLOCK) render_depth_kernel(const unsigned* 
 }
 
 // ---- resolve -----------------------------------------------------------------------------------------------------------------
-// (int)(255 c + 0.5) clamped to 0 .. 255 (a NaN gives 0)
-__device__ __forceinline__ unsigned rn_quant(float c) { return (unsigned)(int)fminf(fmaxf(255.0f * c + 0.5f, 0.0f), 255.0f); }
-
-// shade of pixel (x, y) under face f of one frame (rule 3 of lemo_amd/render.py)
-__device__ __forceinline__ float rn_shade(const float* __restrict__ vf, const float* __restrict__ nf, int V, const int* __restrict__ faces, int f,
-                                          const OcCam& c, const RnShade& sh, int x, int y) {
-  OcXf X = {};
-  OcTri t;
-  float lam = 0.0f;
-  if (oc_face(vf, V, faces, f, X, c, t)) {                    // true for every id the id pass wrote
-    const float dx = oc_ray_x(x, c), dy = oc_ray_y(y, c);
-    const float e0 = (t.e0[0] * dx + t.e0[1] * dy) + t.e0[2];
-    const float e1 = (t.e1[0] * dx + t.e1[1] * dy) + t.e1[2];
-    const float e2 = (t.e2[0] * dx + t.e2[1] * dy) + t.e2[2];
-    const float s = (e0 + e1) + e2;
-    const float b0 = e0 / s, b1 = e1 / s, b2 = e2 / s;
-    const float *n0 = nf + 3 * (size_t)faces[3 * (size_t)f], *n1 = nf + 3 * (size_t)faces[3 * (size_t)f + 1],
-                *n2 = nf + 3 * (size_t)faces[3 * (size_t)f + 2];
-    float n[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) n[k] = (b0 * n0[k] + b1 * n1[k]) + b2 * n2[k];
-    const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
-    if (len > 0.0f) lam = fabsf(n[2]) / len;                  // false also for a NaN
-  }
-  return fminf(1.0f, sh.ambient + sh.diffuse * lam);
-}
-
+// rn_quant and rn_shade (rule 3 of lemo_amd/render.py) live in raster_device.hpp: view_kernels.hip shades with the same functions
 // One thread per group of RN_PPT pixels of the flat [B H W] pixel range.  Group g covers pixels p0 + 4 (g - 1) .. + 3 cut to [0, n):
 // p0 = (address of rgb) mod 4 is the first pixel whose three bytes start on a dword, so every whole group is three aligned dwords
 // whatever the image size and wherever in a larger tensor the frames start; group 0 (the p0 pixels before) and the last group go
