@@ -29,17 +29,6 @@
 #include <cstring>
 #include <new>
 
-// slots of AeEngine::amax.  0 .. AE_SLOT_DYN - 1 are rewritten every step (zeroed by the optimiser launch and at load)
-#define AE_SLOT_ACT(i) (i)                /* max |output of layer i| (forward) */
-#define AE_SLOT_DP(i) (20 + (i))          /* max |d(pre-activation) of layer i| where a convolution wrote it */
-#define AE_SLOT_DPOOL(b) (40 + (b))       /* max |d(pooled output of encoder block b)| */
-#define AE_SLOT_DYN 45
-#define AE_SLOT_X8 45                     /* the clip image */
-#define AE_SLOT_LOSS 46                   /* max (mask / count): the loss gradient is +-1 x that */
-#define AE_SLOT_W(i) (48 + (i))           /* max |weights of layer i| (forward and backward pack hold the same values) */
-#define AE_SLOT_SCRATCH 70
-#define AE_NSLOT 128
-
 namespace lemo {
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -624,12 +613,8 @@ int ae_conv(const float* in, const float* wt, const float* bias, const float* au
 // With ci on the MFMA's row axis a lane holds 4 consecutive ci of one co per accumulator quad: the slab partial is stored with
 // dwordx4 stores, 1 KiB contiguous per wave, directly in the forward pack wt[tap][ci/8][co][8] -- the layout of the parameter
 // vector, so the optimizer reads it with unit stride.
-struct AeWgradJob {
-  const float* dy; const float* x; float* partial; float* dbp;       // dbp: [nslab][2][cout] bias-gradient partials (pixel parity kept apart)
-  int H, W; int cin, cout, nslab, slab_len, nwave;
-};
-// the grid is the layers' waves in the order the host wants them DISPATCHED: the long ones first (full 576-pixel slabs run 23 us),
-// the short ones of the 14 x 9 layers last, so that the launch does not end on a few long waves
+// The grid is the layers' waves (AeWgradJob, ae_wgrad_jobs: ae_engine.hpp) in the order the host wants them DISPATCHED: the long ones
+// first (full 576-pixel slabs run 23 us), the short ones of the 14 x 9 layers last, so that the launch does not end on a few long waves
 struct AeWgradJobs { AeWgradJob j[AE_NLAYER]; int first[AE_NLAYER + 1]; int n; size_t cs; };       // cs: clip stride (clip = blockIdx.y)
 
 template <int MODE>        // 0: the product; diagnostics (tools/ae_wgrad_probe.py): 1 = operands loaded once per wave, 2 = no MFMAs
@@ -934,26 +919,17 @@ int ae_pack_launch(const AePackArgs& A, bool unpack, const float* src, float* ds
 // ---------------------------------------------------------------------------------------------------------------------
 // the engine
 // ---------------------------------------------------------------------------------------------------------------------
-struct AeEngine {
-  int H[6], W[6];
-  AeLayer L[AE_NLAYER];
-  int n_w = 0, n_b = 0, n_wb = 0, n_flat = 0;
-  size_t n_part = 0, n_dbp = 0;
+struct AeEngine : AeNet {        // (the network's buffers are clip 0's)
   float lr = 0.f;
-  // carved from the caller's workspace
+  // carved from the caller's workspace, per clip
   float *theta = nullptr, *m = nullptr, *v = nullptr, *wb = nullptr, *dbp = nullptr, *zero_bias = nullptr, *ctr = nullptr,
-        *part = nullptr, *moc = nullptr, *x8 = nullptr;
-  float* act[AE_NLAYER];       // output of layer i (decoder blocks 0..3: their second layer's output lives stuffed in S[b + 1])
-  float* xin[AE_NLAYER];       // input of layer i
-  float* dp[AE_NLAYER];        // d(pre-activation) of layer i
-  float *P[5], *dP[5], *S[5];
-  unsigned char* idx[5];
+        *part = nullptr, *moc = nullptr;
   hipGraphExec_t exec[2] = {nullptr, nullptr};      // 5 steps, 1 step
   unsigned long long loaded = 0;   // bit c: clip c has been loaded (every clip must be before a step / forward: ADVICE r04)
   int forward_valid = 0;           // an eval forward of all clips ran after the last step / load (what forward_clip(c > 0) copies from)
   int nclip = 1;               // clips side by side: clip c's buffers are the pointers above + c * cs floats
   size_t cs = 0;
-  float* amax = nullptr;       // [AE_NSLOT] per clip: tensor maxima / bounds the split-f16 convolutions scale by (slots below)
+  float* amax = nullptr;       // [AE_NSLOT] per clip: tensor maxima / bounds the split-f16 convolutions scale by (AE_SLOT_*, ae_engine.hpp)
   int f16 = 0;                 // 0: fp32-input MFMA convolutions (shipped) ; 1: split-f16 convolutions (round 6; LEMO_AE_ARITH=f16).  Measured
                                // (profiles/r06_ae_f16_vs_fp32.txt): 16.05 vs 16.4 ms per clip at 8 clips per engine, 14.4 vs 15.45 at 16, but 44.5 vs
                                // 28.8 for a solo clip -- the launches are bound by L2 re-reads of the direct-from-global operands (every input element
@@ -969,99 +945,38 @@ static int ae_slab_scale(int nclip) {
 }
 
 static void ae_layout(AeEngine* e, int H0, int W0, float* base, size_t* total, int slab_scale = 1) {
-  e->H[0] = H0; e->W[0] = W0;
-  for (int k = 0; k < 5; ++k) { e->H[k + 1] = (e->H[k] - 1) / 2 + 1; e->W[k + 1] = (e->W[k] - 1) / 2 + 1; }
-  int n = 0;
-  for (int b = 0; b < 5; ++b) {
-    const int ci = AE_ENC[b][0], co = AE_ENC[b][1];
-    e->L[n++] = AeLayer{ci, co, pad8(ci), pad32(co), 0, b};
-    e->L[n++] = AeLayer{co, co, pad32(co), pad32(co), 0, b};
-  }
-  for (int b = 0; b < 5; ++b) {
-    const int ci = AE_DEC[b][0], co = AE_DEC[b][1];
-    e->L[n++] = AeLayer{ci, co, pad32(ci), pad32(co), 1, 4 - b};
-    e->L[n++] = AeLayer{co, co, pad32(co), pad32(co), 1, 4 - b};
-  }
-  int w = 0, wbo = 0, flat = 0;
-  size_t part = 0, dbp = 0;
-  for (int i = 0; i < AE_NLAYER; ++i) {
-    AeLayer& l = e->L[i];
-    l.w_off = w; w += 9 * l.cin_pad * l.cout_pad;
-    l.wb_off = i == 0 ? -1 : wbo; if (i) wbo += 9 * l.cin_pad * l.cout_pad;      // the first layer needs no backward-data
-    l.flat_w = flat; flat += 9 * l.cin * l.cout;
-    l.flat_b = flat; flat += l.cout;
-    l.nslab = ae_slabs(e->H[l.level], e->W[l.level], &l.slab_len, slab_scale);
-    l.part_off = part; part += (size_t)l.nslab * 9 * l.cin_pad * l.cout_pad;
-    l.dbp_off = dbp; dbp += (size_t)l.nslab * 2 * l.cout_pad;
-  }
-  e->n_w = w; e->n_wb = wbo; e->n_flat = flat; e->n_part = part; e->n_dbp = dbp;
-  int b = 0;
-  for (int i = 0; i < AE_NLAYER; ++i) { e->L[i].b_off = b; b += e->L[i].cout_pad; }
-  e->n_b = b;
+  const AePartials np = ae_net_layers(*e, H0, W0, slab_scale, 1);
   Bump B{base};
   e->theta = B.take(e->n_w + e->n_b); e->m = B.take(e->n_w + e->n_b); e->v = B.take(e->n_w + e->n_b);
-  e->wb = B.take(e->n_wb); e->dbp = B.take(e->n_dbp); e->zero_bias = B.take(256); e->ctr = B.take(64); e->amax = B.take(AE_NSLOT);
-  e->part = B.take(e->n_part); e->moc = B.take((size_t)H0 * W0);
-  e->x8 = B.take(cg8p_floats(8, H0, W0));
-  for (int bk = 0; bk < 5; ++bk) {
-    const int lv = bk, i0 = 2 * bk, i2 = 2 * bk + 1;
-    e->act[i0] = B.take(cg8p_floats(e->L[i0].cout_pad, e->H[lv], e->W[lv]));
-    e->act[i2] = B.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv], e->W[lv]));
-    e->P[bk] = B.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv + 1], e->W[lv + 1]));
-    e->dP[bk] = B.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv + 1], e->W[lv + 1]));
-    e->idx[bk] = reinterpret_cast<unsigned char*>(B.take(((size_t)e->L[i2].cout_pad * e->H[lv + 1] * e->W[lv + 1] + 3) / 4));
-    e->xin[i0] = bk == 0 ? e->x8 : e->P[bk - 1];
-    e->xin[i2] = e->act[i0];
-  }
-  for (int bk = 0; bk < 5; ++bk) {
-    const int lv = 4 - bk, i1 = 10 + 2 * bk;
-    e->S[bk] = B.take(cg8p_floats(e->L[i1].cin_pad, e->H[lv], e->W[lv]));
-  }
-  for (int bk = 0; bk < 5; ++bk) {
-    const int lv = 4 - bk, i1 = 10 + 2 * bk, i2 = 11 + 2 * bk;
-    e->act[i1] = B.take(cg8p_floats(e->L[i1].cout_pad, e->H[lv], e->W[lv]));
-    e->act[i2] = bk < 4 ? e->S[bk + 1] : B.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv], e->W[lv]));
-    e->xin[i1] = e->S[bk];
-    e->xin[i2] = e->act[i1];
-  }
-  for (int i = 0; i < AE_NLAYER; ++i) e->dp[i] = B.take(cg8p_floats(e->L[i].cout_pad, e->H[e->L[i].level], e->W[e->L[i].level]));
+  e->wb = B.take(e->n_wb); e->dbp = B.take(np.dbp); e->zero_bias = B.take(256); e->ctr = B.take(64); e->amax = B.take(AE_NSLOT);
+  e->part = B.take(np.part); e->moc = B.take((size_t)H0 * W0);
+  ae_net_carve_image(*e, B);
   *total = B.off;
 }
 
-// engine launches carry every clip: ae_conv(..., s) -> ae_conv(..., s, 0, 0, 0, e->nclip, e->cs)
-#define AE_CONV(e_, ...) ae_conv(__VA_ARGS__, 0, 0, 0, (e_)->nclip, (e_)->cs)
-// ... with the scale slots of a split-f16 launch: input maximum (x fac: a bound, see the kernel's header), weights of layer LW, output slot
-#define AE_CONVS(e_, SIN, FAC, LW, SOUT, ...)                                                                                   \
-  [&]() { const AeF16 q_{(e_)->amax + (SIN), (e_)->amax + AE_SLOT_W(LW), (e_)->amax + (SOUT), (FAC)};                           \
-          return ae_conv(__VA_ARGS__, 0, 0, 0, (e_)->nclip, (e_)->cs, (e_)->f16 ? &q_ : nullptr); }()
-
-static int ae_forward(AeEngine* e, hipStream_t s) {
-  for (int b = 0; b < 5; ++b) {
-    const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
-    const AeGeo g = geo_plain(H, W);
-    // (pooling and zero stuffing keep the maximum: the pooled / stuffed inputs scale by their source's slot)
-    CHK(AE_CONVS(e, b == 0 ? AE_SLOT_X8 : AE_SLOT_ACT(i0 - 1), 1.f, i0, AE_SLOT_ACT(i0),
-                  e->xin[i0], e->theta + e->L[i0].w_off, e->theta + e->n_w + e->L[i0].b_off, nullptr, e->act[i0], g, e->L[i0].cin_pad, e->L[i0].cout_pad, 0, s));
-    CHK(AE_CONVS(e, AE_SLOT_ACT(i0), 1.f, i2, AE_SLOT_ACT(i2),
-                  e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, 0, s));
-    CHK(maxpool3s2_fwd(e->act[i2], H, W, e->P[b], e->idx[b], e->L[i2].cout_pad, s, e->nclip, e->cs));
-  }
-  CHK(stuff2_fwd(e->P[4], e->H[5], e->W[5], e->S[0], e->H[4], e->W[4], e->L[10].cin_pad, s, e->nclip, e->cs));
-  for (int b = 0; b < 5; ++b) {
-    const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
-    AeGeo g = geo_plain(H, W);
-    CHK(AE_CONVS(e, AE_SLOT_ACT(i1 - 1), 1.f, i1, AE_SLOT_ACT(i1),
-                  e->xin[i1], e->theta + e->L[i1].w_off, e->theta + e->n_w + e->L[i1].b_off, nullptr, e->act[i1], g, e->L[i1].cin_pad, e->L[i1].cout_pad, 0, s));
-    if (b < 4) {       // straight into the stuffed input of the next block: pixel (y, x) -> (2y, 2x) of the next finer level
-      g.out_Wp = e->W[lv - 1] + 2; g.out_HWp = (e->H[lv - 1] + 2) * g.out_Wp; g.out_s = 2;
-    }
-    CHK(AE_CONVS(e, AE_SLOT_ACT(i1), 1.f, i2, AE_SLOT_ACT(i2),
-                  e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, b < 4 ? 0 : 2, s));
-  }
-  return 0;
+// an engine launch carries every clip, each with its own parameters; `site` names the scale slots of a split-f16 launch
+static auto ae_conv_of(AeEngine* e, hipStream_t s) {
+  return [e, s](const AeConvSite& c, const float* in, const float* wt, const float* bias, const float* aux, float* out, const AeGeo& g,
+                int cin, int cout, int epi) {
+    const AeF16 q{e->amax + c.in, e->amax + AE_SLOT_W(c.w), e->amax + c.out, c.fac};
+    return ae_conv(in, wt, bias, aux, out, g, cin, cout, epi, s, 0, 0, 0, e->nclip, e->cs, e->f16 ? &q : nullptr, AE_WCS_CLIP);
+  };
 }
 
-static int ae_wgrad_launch(AeEngine* e, hipStream_t s, int mode);
+static int ae_forward(AeEngine* e, hipStream_t s) { return ae_net_forward(*e, e->theta, AeBatch{e->nclip, e->cs, s}, ae_conv_of(e, s)); }
+
+static int ae_wgrad_launch(AeEngine* e, hipStream_t s, int mode) {
+  AeWgradJobs J;
+  const AeWgradCount c = ae_wgrad_jobs(*e, e->part, e->dbp, J.j, J.first);
+  J.n = c.n; J.cs = e->cs;
+  const dim3 grid(c.nb, e->nclip);
+  if (mode == 1) hipLaunchKernelGGL(ae_wgrad_multi_kernel<1>, grid, dim3(64), 0, s, J);
+  else if (mode == 2) hipLaunchKernelGGL(ae_wgrad_multi_kernel<2>, grid, dim3(64), 0, s, J);
+  else if (mode == 3) hipLaunchKernelGGL(ae_wgrad_multi_kernel<3>, grid, dim3(64), 0, s, J);
+  else if (mode == 4) hipLaunchKernelGGL(ae_wgrad_multi_kernel<4>, grid, dim3(64), 0, s, J);
+  else hipLaunchKernelGGL(ae_wgrad_multi_kernel<0>, grid, dim3(64), 0, s, J);
+  return (int)hipGetLastError();
+}
 
 static int ae_train_step(AeEngine* e, hipStream_t s) {
   CHK(ae_forward(e, s));
@@ -1069,81 +984,9 @@ static int ae_train_step(AeEngine* e, hipStream_t s) {
   hipLaunchKernelGGL(ae_loss_grad_kernel, dim3((H0 * W0 + 255) / 256, e->nclip), dim3(256), 0, s, (const float*)e->act[19], (const float*)e->x8,
                      (const float*)e->moc, e->dp[19], H0, W0, e->ctr, lr_decimal(e->lr), e->cs);
   CHK((int)hipGetLastError());
-  // ---- decoder, last block first
-  for (int b = 4; b >= 0; --b) {
-    const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
-    const AeGeo g = geo_plain(H, W);
-    CHK(AE_CONVS(e, i2 == 19 ? AE_SLOT_LOSS : AE_SLOT_DP(i2), 1.f, i2, AE_SLOT_DP(i1),
-                  e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i1], e->dp[i1], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));     // * lrelu'(act[i1])
-    // adjoint of (stuffing, transposed conv): only the even pixels of d(stuffed input) exist downstream -> enumerate the
-    // coarse grid, centre taps at (2i, 2j); times lrelu' of the previous block's output (read where it lives: stuffed in S[b])
-    const int h = e->H[lv + 1], w = e->W[lv + 1];
-    AeGeo gs = geo_plain(h, w);
-    gs.in_Wp = W + 2; gs.in_HWp = (H + 2) * (W + 2); gs.in_s = 2;
-    gs.aux_Wp = gs.in_Wp; gs.aux_HWp = gs.in_HWp; gs.aux_s = 2;
-    float* dst = b > 0 ? e->dp[i1 - 1] : e->dP[4];
-    if (b > 0) CHK(AE_CONVS(e, AE_SLOT_DP(i1), 1.f, i1, AE_SLOT_DP(i1 - 1),
-                             e->dp[i1], e->wb + e->L[i1].wb_off, nullptr, e->S[b], dst, gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 1, s));
-    else       CHK(AE_CONVS(e, AE_SLOT_DP(i1), 1.f, i1, AE_SLOT_DPOOL(4),
-                             e->dp[i1], e->wb + e->L[i1].wb_off, e->zero_bias, nullptr, dst, gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 2, s));   // the latent has no activation
-  }
-  // ---- encoder, last block first
-  for (int b = 4; b >= 0; --b) {
-    const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
-    const AeGeo g = geo_plain(H, W);
-    CHK(maxpool3s2_bwd(e->dP[b], e->idx[b], e->act[i2], e->dp[i2], H, W, e->L[i2].cout_pad, s, e->nclip, e->cs));
-    // (the max-pool adjoint adds at most four window gradients into one pixel, times lrelu' <= 1: dp[i2] is bounded by 4 x the pooled gradient's maximum)
-    CHK(AE_CONVS(e, AE_SLOT_DPOOL(b), 4.f, i2, AE_SLOT_DP(i0),
-                  e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i0], e->dp[i0], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
-    if (b > 0) CHK(AE_CONVS(e, AE_SLOT_DP(i0), 1.f, i0, AE_SLOT_DPOOL(b - 1),
-                             e->dp[i0], e->wb + e->L[i0].wb_off, e->zero_bias, nullptr, e->dP[b - 1], g, e->L[i0].cout_pad, e->L[i0].cin_pad, 2, s));
-  }
-  // ---- all weight and bias gradients
-  CHK(ae_wgrad_launch(e, s, 0));
-  // ---- Adam
-  AeAdamArgs A;
-  for (int i = 0; i < AE_NLAYER; ++i) {
-    const AeLayer& l = e->L[i];
-    A.L[i] = AeAdamLayer{e->part + l.part_off, e->dbp + l.dbp_off, l.nslab, l.w_off, l.b_off, l.wb_off, ilog2(l.cin_pad / 8), ilog2(l.cout_pad), l.cin, l.cout};
-  }
-  A.theta = e->theta; A.m = e->m; A.v = e->v; A.wb = e->wb; A.ctr = e->ctr; A.amax = e->amax;
-  A.n_w = e->n_w; A.n_all = e->n_w + e->n_b; A.lr = e->lr; A.cs = e->cs;
-  hipLaunchKernelGGL(ae_adam_kernel, dim3((A.n_all / 4 + 255) / 256, e->nclip), dim3(256), 0, s, A);        // (n_w and n_b are multiples of 4)
-  return (int)hipGetLastError();
-}
-
-static int ae_wgrad_launch(AeEngine* e, hipStream_t s, int mode) {
-  AeWgradJobs J;
-  int nb = 0, n = 0;
-  for (int lv = 0; lv < 5; ++lv)                                // dispatch order: big images (long waves) first
-    for (int i = 0; i < AE_NLAYER; ++i) {
-      const AeLayer& l = e->L[i];
-      if (l.level != lv) continue;
-      AeWgradJob& q = J.j[n];
-      q.dy = e->dp[i]; q.x = e->xin[i]; q.partial = e->part + l.part_off; q.dbp = e->dbp + l.dbp_off;
-      q.H = e->H[l.level]; q.W = e->W[l.level];
-      q.cin = l.cin_pad; q.cout = l.cout_pad; q.nslab = l.nslab; q.slab_len = l.slab_len;
-      q.nwave = 3 * l.nslab * (l.cout_pad / 32) * ((l.cin_pad + 31) / 32);
-      J.first[n++] = nb;
-      nb += q.nwave;
-    }
-  J.first[n] = nb; J.n = n; J.cs = e->cs;
-  if (mode == 1) hipLaunchKernelGGL(ae_wgrad_multi_kernel<1>, dim3(nb, e->nclip), dim3(64), 0, s, J);
-  else if (mode == 2) hipLaunchKernelGGL(ae_wgrad_multi_kernel<2>, dim3(nb, e->nclip), dim3(64), 0, s, J);
-  else if (mode == 3) hipLaunchKernelGGL(ae_wgrad_multi_kernel<3>, dim3(nb, e->nclip), dim3(64), 0, s, J);
-  else if (mode == 4) hipLaunchKernelGGL(ae_wgrad_multi_kernel<4>, dim3(nb, e->nclip), dim3(64), 0, s, J);
-  else hipLaunchKernelGGL(ae_wgrad_multi_kernel<0>, dim3(nb, e->nclip), dim3(64), 0, s, J);
-  return (int)hipGetLastError();
-}
-
-static AePackArgs ae_pack_args(const AeEngine* e) {
-  AePackArgs A;
-  for (int i = 0; i < AE_NLAYER; ++i) {
-    const AeLayer& l = e->L[i];
-    A.L[i] = AePackLayer{l.w_off, l.wb_off, l.b_off, l.flat_w, l.flat_b, ilog2(l.cin_pad / 8), ilog2(l.cout_pad), l.cin, l.cout, l.deconv};
-  }
-  A.n_w = e->n_w; A.n_all = e->n_w + e->n_b;
-  return A;
+  CHK(ae_net_backward_data(*e, e->wb, e->zero_bias, AeBatch{e->nclip, e->cs, s}, ae_conv_of(e, s)));
+  CHK(ae_wgrad_launch(e, s, 0));           // all weight and bias gradients
+  return ae_adam_launch(ae_adam_args(*e, e->part, e->dbp, 1, e->theta, e->m, e->v, e->wb, e->ctr, e->amax, e->lr, e->cs), e->nclip, s);
 }
 
 static int ae_capture(AeEngine* e, hipStream_t s, int steps, hipGraphExec_t* out) {
@@ -1169,10 +1012,9 @@ long long lemo_ae_ws_floats(int H, int W) {
 }
 
 int lemo_ae_n_param(void) {
-  AeEngine e;
-  size_t total = 0;
-  ae_layout(&e, 64, 64, nullptr, &total);
-  return e.n_flat;
+  AeNet n;
+  ae_net_layers(n, 64, 64, 1, 1);          // (the parameter count does not depend on the image size)
+  return n.n_flat;
 }
 
 void* lemo_ae_create(const lemo_ae_desc* d) {
@@ -1203,7 +1045,7 @@ int lemo_ae_load_clip(void* h, int clip, const float* flat, const float* x, cons
   hipStream_t s = (hipStream_t)stream;
   const int n_all = e->n_w + e->n_b, H = e->H[0], W = e->W[0];
   const size_t o = (size_t)clip * e->cs;
-  hipLaunchKernelGGL((ae_pack_kernel<false>), dim3((n_all + 255) / 256), dim3(256), 0, s, ae_pack_args(e), flat, e->theta + o, e->wb + o);
+  hipLaunchKernelGGL((ae_pack_kernel<false>), dim3((n_all + 255) / 256), dim3(256), 0, s, ae_pack_args(*e), flat, e->theta + o, e->wb + o);
   int rc = (int)hipGetLastError();
   if (rc) return rc;
   if ((rc = (int)hipMemsetAsync(e->m + o, 0, sizeof(float) * n_all, s))) return rc;        // a fresh optimizer (opt_amass_temp.py:160-164)
@@ -1273,7 +1115,7 @@ int lemo_ae_params_clip(void* h, int clip, float* flat_out, void* stream) {
   if (!e || !flat_out || clip < 0 || clip >= e->nclip) return LEMO_ERR_ARG;
   if (!(e->loaded >> clip & 1ull)) return LEMO_ERR_STATE;
   const int n_all = e->n_w + e->n_b;
-  hipLaunchKernelGGL((ae_pack_kernel<true>), dim3((n_all + 255) / 256), dim3(256), 0, (hipStream_t)stream, ae_pack_args(e),
+  hipLaunchKernelGGL((ae_pack_kernel<true>), dim3((n_all + 255) / 256), dim3(256), 0, (hipStream_t)stream, ae_pack_args(*e),
                      (const float*)e->theta + (size_t)clip * e->cs, flat_out, (float*)nullptr);
   return (int)hipGetLastError();
 }

@@ -26,11 +26,8 @@
 
 namespace lemo {
 
-struct AetWgradJob {
-  const float* dy; const float* x; float* partial; float* dbp;       // image 0's operands; partial [group][slab][9 cin cout], dbp [group][slab][2][cout]
-  int H, W; int cin, cout, nslab, slab_len, nwave;
-};
-struct AetWgradJobs { AetWgradJob j[AE_NLAYER]; int first[AE_NLAYER + 1]; int n; int bs, groups; size_t cs; };
+// jobs: image 0's operands; partial [group][slab][9 cin cout], dbp [group][slab][2][cout]
+struct AetWgradJobs { AeWgradJob j[AE_NLAYER]; int first[AE_NLAYER + 1]; int n; int bs, groups; size_t cs; };
 
 // One wave = one 32 (ci) x 32 (co) tile, one kernel row, one pixel slab, one image group (blockIdx.y): the images of the group one
 // after the other into the same accumulators (image order, then pixel order: deterministic).  Per image the loop is
@@ -40,7 +37,7 @@ __global__ void __launch_bounds__(64)
 aet_wgrad_kernel(AetWgradJobs J) {
   int k = 0;
   while (k + 1 < J.n && (int)blockIdx.x >= J.first[k + 1]) ++k;               // block -> layer (uniform)
-  const AetWgradJob& q = J.j[k];
+  const AeWgradJob& q = J.j[k];
   int tile = (int)blockIdx.x - J.first[k];                         // (slab, co tile, ci tile, kernel row)
   const int lane = threadIdx.x;
   const int Wp = q.W + 2, HWp = (q.H + 2) * Wp;
@@ -250,22 +247,13 @@ aet_grad_kernel(AeAdamArgs A, float* __restrict__ gpk) {
 // ---------------------------------------------------------------------------------------------------------------------
 // the engine
 // ---------------------------------------------------------------------------------------------------------------------
-struct AetEngine {
-  int H[6], W[6], bs = 1, groups = 1;
-  AeLayer L[AE_NLAYER];
-  int n_w = 0, n_b = 0, n_wb = 0, n_flat = 0;
+struct AetEngine : AeNet {       // (the network's buffers are image 0's; image c's are `c * cs` floats further)
+  int bs = 1, groups = 1;
   double lr = 0.0; float lr_f = 0.f, w_body = 10.f, w_v = 10.f, w_c = 1.f;
   int use_graph = 0, loaded = 0, nblk = 0;
   // shared by the batch
   float *theta = nullptr, *m = nullptr, *v = nullptr, *wb = nullptr, *dbp = nullptr, *part = nullptr, *zero_bias = nullptr,
         *ctr = nullptr, *amax = nullptr, *gpk = nullptr, *lpart = nullptr, *losses = nullptr, *ybuf = nullptr;
-  // image 0's buffers; image c's are `c * cs` floats further
-  float *x8 = nullptr;
-  float* act[AE_NLAYER];
-  float* xin[AE_NLAYER];
-  float* dp[AE_NLAYER];
-  float *P[5], *dP[5], *S[5];
-  unsigned char* idx[5];
   size_t cs = 0;
   hipGraphExec_t exec = nullptr;
   hipGraphExec_t exec_ep[2] = {nullptr, nullptr};      // one step of an epoch (assemble, step, log): [0] evaluation, [1] training
@@ -279,86 +267,27 @@ static bool aet_shape_ok(int H, int W, int bs) {
 static void aet_layout(AetEngine* e, int H0, int W0, int bs, float* base, size_t* total) {
   e->bs = bs;
   e->groups = bs < AET_GROUPS ? bs : AET_GROUPS;
-  e->H[0] = H0; e->W[0] = W0;
-  for (int k = 0; k < 5; ++k) { e->H[k + 1] = (e->H[k] - 1) / 2 + 1; e->W[k + 1] = (e->W[k] - 1) / 2 + 1; }
-  int n = 0;
-  for (int b = 0; b < 5; ++b) {
-    const int ci = AE_ENC[b][0], co = AE_ENC[b][1];
-    e->L[n++] = AeLayer{ci, co, pad8(ci), pad32(co), 0, b};
-    e->L[n++] = AeLayer{co, co, pad32(co), pad32(co), 0, b};
-  }
-  for (int b = 0; b < 5; ++b) {
-    const int ci = AE_DEC[b][0], co = AE_DEC[b][1];
-    e->L[n++] = AeLayer{ci, co, pad32(ci), pad32(co), 1, 4 - b};
-    e->L[n++] = AeLayer{co, co, pad32(co), pad32(co), 1, 4 - b};
-  }
-  int w = 0, wbo = 0, flat = 0, b = 0;
-  size_t part = 0, dbp = 0;
-  for (int i = 0; i < AE_NLAYER; ++i) {
-    AeLayer& l = e->L[i];
-    l.w_off = w; w += 9 * l.cin_pad * l.cout_pad;
-    l.wb_off = i == 0 ? -1 : wbo; if (i) wbo += 9 * l.cin_pad * l.cout_pad;
-    l.flat_w = flat; flat += 9 * l.cin * l.cout;
-    l.flat_b = flat; flat += l.cout;
-    l.nslab = ae_slabs(e->H[l.level], e->W[l.level], &l.slab_len);
-    l.part_off = part; part += (size_t)e->groups * l.nslab * 9 * l.cin_pad * l.cout_pad;
-    l.dbp_off = dbp; dbp += (size_t)e->groups * l.nslab * 2 * l.cout_pad;
-  }
-  for (int i = 0; i < AE_NLAYER; ++i) { e->L[i].b_off = b; b += e->L[i].cout_pad; }
-  e->n_w = w; e->n_b = b; e->n_wb = wbo; e->n_flat = flat;
+  const AePartials np = ae_net_layers(*e, H0, W0, 1, e->groups);
   e->nblk = bs * ((H0 * W0 + AET_LOSS_BLOCK - 1) / AET_LOSS_BLOCK);
   Bump B{base};
   e->theta = B.take(e->n_w + e->n_b); e->m = B.take(e->n_w + e->n_b); e->v = B.take(e->n_w + e->n_b); e->gpk = B.take(e->n_w + e->n_b);
-  e->wb = B.take(e->n_wb); e->dbp = B.take(dbp); e->part = B.take(part);
+  e->wb = B.take(e->n_wb); e->dbp = B.take(np.dbp); e->part = B.take(np.part);
   e->zero_bias = B.take(256); e->ctr = B.take(64); e->amax = B.take(64); e->losses = B.take(64);
   e->lpart = B.take((size_t)e->nblk * 3); e->ybuf = B.take((size_t)bs * H0 * W0);
   const size_t shared = B.off;
   Bump I{base ? base + shared : nullptr};
-  e->x8 = I.take(cg8p_floats(8, H0, W0));
-  for (int bk = 0; bk < 5; ++bk) {
-    const int lv = bk, i0 = 2 * bk, i2 = 2 * bk + 1;
-    e->act[i0] = I.take(cg8p_floats(e->L[i0].cout_pad, e->H[lv], e->W[lv]));
-    e->act[i2] = I.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv], e->W[lv]));
-    e->P[bk] = I.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv + 1], e->W[lv + 1]));
-    e->dP[bk] = I.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv + 1], e->W[lv + 1]));
-    e->idx[bk] = reinterpret_cast<unsigned char*>(I.take(((size_t)e->L[i2].cout_pad * e->H[lv + 1] * e->W[lv + 1] + 3) / 4));
-    e->xin[i0] = bk == 0 ? e->x8 : e->P[bk - 1];
-    e->xin[i2] = e->act[i0];
-  }
-  for (int bk = 0; bk < 5; ++bk) e->S[bk] = I.take(cg8p_floats(e->L[10 + 2 * bk].cin_pad, e->H[4 - bk], e->W[4 - bk]));
-  for (int bk = 0; bk < 5; ++bk) {
-    const int lv = 4 - bk, i1 = 10 + 2 * bk, i2 = 11 + 2 * bk;
-    e->act[i1] = I.take(cg8p_floats(e->L[i1].cout_pad, e->H[lv], e->W[lv]));
-    e->act[i2] = bk < 4 ? e->S[bk + 1] : I.take(cg8p_floats(e->L[i2].cout_pad, e->H[lv], e->W[lv]));
-    e->xin[i1] = e->S[bk];
-    e->xin[i2] = e->act[i1];
-  }
-  for (int i = 0; i < AE_NLAYER; ++i) e->dp[i] = I.take(cg8p_floats(e->L[i].cout_pad, e->H[e->L[i].level], e->W[e->L[i].level]));
+  ae_net_carve_image(*e, I);
   e->cs = I.off;
   *total = shared + (size_t)bs * I.off;
 }
 
-// every launch carries the batch (clip dimension = image) with one parameter set (weight stride 0)
-#define AET_CONV(e_, ...) ae_conv(__VA_ARGS__, 0, 0, 0, (e_)->bs, (e_)->cs, nullptr, 0)
-
-static int aet_forward(AetEngine* e, hipStream_t s) {
-  for (int b = 0; b < 5; ++b) {
-    const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
-    const AeGeo g = geo_plain(H, W);
-    CHK(AET_CONV(e, e->xin[i0], e->theta + e->L[i0].w_off, e->theta + e->n_w + e->L[i0].b_off, nullptr, e->act[i0], g, e->L[i0].cin_pad, e->L[i0].cout_pad, 0, s));
-    CHK(AET_CONV(e, e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, 0, s));
-    CHK(maxpool3s2_fwd(e->act[i2], H, W, e->P[b], e->idx[b], e->L[i2].cout_pad, s, e->bs, e->cs));
-  }
-  CHK(stuff2_fwd(e->P[4], e->H[5], e->W[5], e->S[0], e->H[4], e->W[4], e->L[10].cin_pad, s, e->bs, e->cs));
-  for (int b = 0; b < 5; ++b) {
-    const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
-    AeGeo g = geo_plain(H, W);
-    CHK(AET_CONV(e, e->xin[i1], e->theta + e->L[i1].w_off, e->theta + e->n_w + e->L[i1].b_off, nullptr, e->act[i1], g, e->L[i1].cin_pad, e->L[i1].cout_pad, 0, s));
-    if (b < 4) { g.out_Wp = e->W[lv - 1] + 2; g.out_HWp = (e->H[lv - 1] + 2) * g.out_Wp; g.out_s = 2; }     // into the next block's stuffed input
-    CHK(AET_CONV(e, e->xin[i2], e->theta + e->L[i2].w_off, e->theta + e->n_w + e->L[i2].b_off, nullptr, e->act[i2], g, e->L[i2].cin_pad, e->L[i2].cout_pad, b < 4 ? 0 : 2, s));
-  }
-  return 0;
+// every launch carries the batch (clip dimension = image) with one parameter set (weight stride 0) and no split-f16 scale slots
+static auto aet_conv_of(AetEngine* e, hipStream_t s) {
+  return [e, s](const AeConvSite&, const float* in, const float* wt, const float* bias, const float* aux, float* out, const AeGeo& g,
+                int cin, int cout, int epi) { return ae_conv(in, wt, bias, aux, out, g, cin, cout, epi, s, 0, 0, 0, e->bs, e->cs, nullptr, 0); };
 }
+
+static int aet_forward(AetEngine* e, hipStream_t s) { return ae_net_forward(*e, e->theta, AeBatch{e->bs, e->cs, s}, aet_conv_of(e, s)); }
 
 static int aet_loss(AetEngine* e, bool step, hipStream_t s) {
   const int H = e->H[0], W = e->W[0];
@@ -372,72 +301,23 @@ static int aet_loss(AetEngine* e, bool step, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+// the optimiser sums a layer's partials over (group, slab); one parameter set: no clip stride
 static AeAdamArgs aet_adam_args(const AetEngine* e) {
-  AeAdamArgs A;
-  for (int i = 0; i < AE_NLAYER; ++i) {
-    const AeLayer& l = e->L[i];
-    A.L[i] = AeAdamLayer{e->part + l.part_off, e->dbp + l.dbp_off, e->groups * l.nslab, l.w_off, l.b_off, l.wb_off,
-                         ilog2(l.cin_pad / 8), ilog2(l.cout_pad), l.cin, l.cout};
-  }
-  A.theta = e->theta; A.m = e->m; A.v = e->v; A.wb = e->wb; A.ctr = e->ctr; A.amax = e->amax;
-  A.n_w = e->n_w; A.n_all = e->n_w + e->n_b; A.lr = e->lr_f; A.cs = 0;
-  return A;
-}
-
-static AePackArgs aet_pack_args(const AetEngine* e) {
-  AePackArgs A;
-  for (int i = 0; i < AE_NLAYER; ++i) {
-    const AeLayer& l = e->L[i];
-    A.L[i] = AePackLayer{l.w_off, l.wb_off, l.b_off, l.flat_w, l.flat_b, ilog2(l.cin_pad / 8), ilog2(l.cout_pad), l.cin, l.cout, l.deconv};
-  }
-  A.n_w = e->n_w; A.n_all = e->n_w + e->n_b;
-  return A;
+  return ae_adam_args(*e, e->part, e->dbp, e->groups, e->theta, e->m, e->v, e->wb, e->ctr, e->amax, e->lr_f, 0);
 }
 
 static int aet_wgrad(AetEngine* e, hipStream_t s) {
   AetWgradJobs J;
-  int nb = 0, n = 0;
-  for (int lv = 0; lv < 5; ++lv)                                // dispatch order: big images (long waves) first
-    for (int i = 0; i < AE_NLAYER; ++i) {
-      const AeLayer& l = e->L[i];
-      if (l.level != lv) continue;
-      AetWgradJob& q = J.j[n];
-      q.dy = e->dp[i]; q.x = e->xin[i]; q.partial = e->part + l.part_off; q.dbp = e->dbp + l.dbp_off;
-      q.H = e->H[l.level]; q.W = e->W[l.level];
-      q.cin = l.cin_pad; q.cout = l.cout_pad; q.nslab = l.nslab; q.slab_len = l.slab_len;
-      q.nwave = 3 * l.nslab * (l.cout_pad / 32) * ((l.cin_pad + 31) / 32);
-      J.first[n++] = nb;
-      nb += q.nwave;
-    }
-  J.first[n] = nb; J.n = n; J.bs = e->bs; J.groups = e->groups; J.cs = e->cs;
-  hipLaunchKernelGGL(aet_wgrad_kernel, dim3(nb, e->groups), dim3(64), 0, s, J);
+  const AeWgradCount c = ae_wgrad_jobs(*e, e->part, e->dbp, J.j, J.first);
+  J.n = c.n; J.bs = e->bs; J.groups = e->groups; J.cs = e->cs;
+  hipLaunchKernelGGL(aet_wgrad_kernel, dim3(c.nb, e->groups), dim3(64), 0, s, J);
   return (int)hipGetLastError();
 }
 
 static int aet_train_step(AetEngine* e, hipStream_t s) {
   CHK(aet_forward(e, s));
   CHK(aet_loss(e, true, s));
-  // ---- decoder, last block first
-  for (int b = 4; b >= 0; --b) {
-    const int lv = 4 - b, H = e->H[lv], W = e->W[lv], i1 = 10 + 2 * b, i2 = 11 + 2 * b;
-    const AeGeo g = geo_plain(H, W);
-    CHK(AET_CONV(e, e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i1], e->dp[i1], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
-    // adjoint of (stuffing, transposed conv): the coarse grid, centre taps at (2i, 2j), times lrelu' of the previous block's output
-    const int h = e->H[lv + 1], w = e->W[lv + 1];
-    AeGeo gs = geo_plain(h, w);
-    gs.in_Wp = W + 2; gs.in_HWp = (H + 2) * (W + 2); gs.in_s = 2;
-    gs.aux_Wp = gs.in_Wp; gs.aux_HWp = gs.in_HWp; gs.aux_s = 2;
-    if (b > 0) CHK(AET_CONV(e, e->dp[i1], e->wb + e->L[i1].wb_off, nullptr, e->S[b], e->dp[i1 - 1], gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 1, s));
-    else       CHK(AET_CONV(e, e->dp[i1], e->wb + e->L[i1].wb_off, e->zero_bias, nullptr, e->dP[4], gs, e->L[i1].cout_pad, e->L[i1].cin_pad, 2, s));
-  }
-  // ---- encoder, last block first
-  for (int b = 4; b >= 0; --b) {
-    const int H = e->H[b], W = e->W[b], i0 = 2 * b, i2 = 2 * b + 1;
-    const AeGeo g = geo_plain(H, W);
-    CHK(maxpool3s2_bwd(e->dP[b], e->idx[b], e->act[i2], e->dp[i2], H, W, e->L[i2].cout_pad, s, e->bs, e->cs));
-    CHK(AET_CONV(e, e->dp[i2], e->wb + e->L[i2].wb_off, nullptr, e->act[i0], e->dp[i0], g, e->L[i2].cout_pad, e->L[i2].cin_pad, 1, s));
-    if (b > 0) CHK(AET_CONV(e, e->dp[i0], e->wb + e->L[i0].wb_off, e->zero_bias, nullptr, e->dP[b - 1], g, e->L[i0].cout_pad, e->L[i0].cin_pad, 2, s));
-  }
+  CHK(ae_net_backward_data(*e, e->wb, e->zero_bias, AeBatch{e->bs, e->cs, s}, aet_conv_of(e, s)));
   CHK(aet_wgrad(e, s));
   return ae_adam_launch(aet_adam_args(e), 1, s);
 }
@@ -449,8 +329,6 @@ static int aet_stage(AetEngine* e, const float* x, const float* y, hipStream_t s
 }
 
 // ---- the loop level: an epoch of different batches assembled on the device (train_epoch.hpp)
-static EpochBlock* aet_block(AetEngine* e) { return reinterpret_cast<EpochBlock*>(e->ctr + EP_BLOCK_OFF); }
-
 // the descriptor's shape rules (the index VALUES live on the device: the caller validates them, lemo_amd/infill_train.py does)
 static int aet_epoch_block(const AetEngine* e, const lemo_aetrain_epoch_desc* d, EpochBlock* B) {
   if (!d || !d->data || !d->idx || d->n_clips < 1 || d->n_steps < 1) return LEMO_ERR_ARG;
@@ -467,14 +345,14 @@ static int aet_epoch_block(const AetEngine* e, const lemo_aetrain_epoch_desc* d,
 
 // one step of an epoch: every kernel reads the step from the device-side cursor
 static int aet_epoch_step(AetEngine* e, bool train, hipStream_t s) {
-  CHK(aet_assemble(EpochBlock{}, aet_block(e), 0, e->x8, e->cs, e->ybuf, e->bs, e->H[0], e->W[0], s));
+  CHK(aet_assemble(EpochBlock{}, ep_block(e->ctr), 0, e->x8, e->cs, e->ybuf, e->bs, e->H[0], e->W[0], s));
   if (train) {
     CHK(aet_train_step(e, s));
   } else {
     CHK(aet_forward(e, s));
     CHK(aet_loss(e, false, s));
   }
-  return ep_end(aet_block(e), e->losses, 4, s);
+  return ep_end(ep_block(e->ctr), e->losses, 4, s);
 }
 
 }  // namespace lemo
@@ -518,7 +396,7 @@ int lemo_aetrain_load(void* h, const float* flat, void* stream) {
   if (!e || !flat) return LEMO_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const size_t n_all = (size_t)e->n_w + e->n_b;
-  CHK(ae_pack_launch(aet_pack_args(e), false, flat, e->theta, e->wb, s));
+  CHK(ae_pack_launch(ae_pack_args(*e), false, flat, e->theta, e->wb, s));
   CHK((int)hipMemsetAsync(e->m, 0, sizeof(float) * n_all, s));          // a fresh optimizer
   CHK((int)hipMemsetAsync(e->v, 0, sizeof(float) * n_all, s));
   CHK((int)hipMemsetAsync(e->ctr, 0, sizeof(float) * 64, s));
@@ -565,7 +443,7 @@ int lemo_aetrain_params(void* h, float* flat_out, void* stream) {
   AetEngine* e = (AetEngine*)h;
   if (!e || !flat_out) return LEMO_ERR_ARG;
   if (!e->loaded) return LEMO_ERR_STATE;
-  return ae_pack_launch(aet_pack_args(e), true, e->theta, flat_out, nullptr, (hipStream_t)stream);
+  return ae_pack_launch(ae_pack_args(*e), true, e->theta, flat_out, nullptr, (hipStream_t)stream);
 }
 
 int lemo_aetrain_grads(void* h, float* flat_out, void* stream) {
@@ -576,7 +454,7 @@ int lemo_aetrain_grads(void* h, float* flat_out, void* stream) {
   const AeAdamArgs A = aet_adam_args(e);
   hipLaunchKernelGGL(aet_grad_kernel, dim3((A.n_all + 255) / 256), dim3(256), 0, s, A, e->gpk);
   CHK((int)hipGetLastError());
-  return ae_pack_launch(aet_pack_args(e), true, e->gpk, flat_out, nullptr, s);
+  return ae_pack_launch(ae_pack_args(*e), true, e->gpk, flat_out, nullptr, s);
 }
 
 int lemo_aetrain_epoch(void* h, const lemo_aetrain_epoch_desc* d, void* stream) {
@@ -587,7 +465,7 @@ int lemo_aetrain_epoch(void* h, const lemo_aetrain_epoch_desc* d, void* stream) 
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const bool train = d->train != 0;
-  CHK(ep_begin(B, aet_block(e), s));
+  CHK(ep_begin(B, ep_block(e->ctr), s));
   if (e->use_graph && !e->exec_ep[train]) CHK(capture_graph(&e->exec_ep[train], s, false, [&] { return aet_epoch_step(e, train, s); }));
   for (int i = 0; i < d->n_steps; ++i) {
     if (e->use_graph) CHK((int)hipGraphLaunch(e->exec_ep[train], s));
@@ -606,10 +484,9 @@ int lemo_aetrain_batch(void* h, const lemo_aetrain_epoch_desc* d, int step, floa
 }
 
 long long lemo_aetrain_state_floats(void) {
-  AetEngine e;
-  size_t total = 0;
-  aet_layout(&e, 8, 8, 1, nullptr, &total);
-  return 3ll * e.n_flat + 2;
+  AeNet n;
+  ae_net_layers(n, 8, 8, 1, 1);            // (the parameter count does not depend on the image size)
+  return 3ll * n.n_flat + 2;
 }
 
 int lemo_aetrain_state_save(void* h, float* out, void* stream) {
@@ -617,7 +494,7 @@ int lemo_aetrain_state_save(void* h, float* out, void* stream) {
   if (!e || !out) return LEMO_ERR_ARG;
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
-  const AePackArgs P = aet_pack_args(e);
+  const AePackArgs P = ae_pack_args(*e);
   CHK(ae_pack_launch(P, true, e->theta, out, nullptr, s));
   CHK(ae_pack_launch(P, true, e->m, out + e->n_flat, nullptr, s));
   CHK(ae_pack_launch(P, true, e->v, out + 2 * (size_t)e->n_flat, nullptr, s));
@@ -628,7 +505,7 @@ int lemo_aetrain_state_load(void* h, const float* in, void* stream) {
   AetEngine* e = (AetEngine*)h;
   if (!e || !in) return LEMO_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const AePackArgs P = aet_pack_args(e);
+  const AePackArgs P = ae_pack_args(*e);
   // the moments take the parameters' packing; the backward pack it writes on the way goes to the gradient scratch (gpk holds
   // n_w + n_b >= n_wb floats and is rewritten by every lemo_aetrain_grads), then the parameters' own backward pack to wb
   CHK(ae_pack_launch(P, false, in + e->n_flat, e->m, e->gpk, s));

@@ -159,8 +159,6 @@ static int sp_run(SpEngine* e, hipStream_t s, bool train) {
 }
 
 // ---- the loop level: an epoch of different batches assembled on the device (train_epoch.hpp)
-static EpochBlock* sp_block(SpEngine* e) { return reinterpret_cast<EpochBlock*>(e->ctr + EP_BLOCK_OFF); }
-
 static int sp_epoch_block(const SpEngine* e, const lemo_sptrain_epoch_desc* d, EpochBlock* B) {
   if (!d || !d->data || !d->idx || d->n_clips < 1 || d->n_steps < 1) return LEMO_ERR_ARG;
   if (e->W - 16 < 9 || e->H < 4) return LEMO_ERR_SHAPE;            // reflect padding by (8, 1) needs more than 8 velocity frames, 2 rows
@@ -169,9 +167,9 @@ static int sp_epoch_block(const SpEngine* e, const lemo_sptrain_epoch_desc* d, E
 }
 
 static int sp_epoch_step(SpEngine* e, bool train, hipStream_t s) {
-  CHK(sp_assemble(EpochBlock{}, sp_block(e), 0, e->xin, e->bs, e->H, e->W, s));
+  CHK(sp_assemble(EpochBlock{}, ep_block(e->ctr), 0, e->xin, e->bs, e->H, e->W, s));
   CHK(sp_run(e, s, train));
-  return ep_end(sp_block(e), e->losses, 3, s);
+  return ep_end(ep_block(e->ctr), e->losses, 3, s);
 }
 
 }  // namespace lemo
@@ -285,7 +283,7 @@ int lemo_sptrain_epoch(void* h, const lemo_sptrain_epoch_desc* d, void* stream) 
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const bool train = d->train != 0;
-  CHK(ep_begin(B, sp_block(e), s));
+  CHK(ep_begin(B, ep_block(e->ctr), s));
   if (e->use_graph && !e->exec_ep[train]) CHK(capture_graph(&e->exec_ep[train], s, false, [&] { return sp_epoch_step(e, train, s); }));
   for (int i = 0; i < d->n_steps; ++i) {
     if (e->use_graph) CHK((int)hipGraphLaunch(e->exec_ep[train], s));

@@ -22,6 +22,7 @@ struct EpochBlock {
   int n_clips, n_masks, mask_len, n_steps, recipe, cursor;
 };
 static_assert(sizeof(EpochBlock) <= (64 - EP_BLOCK_OFF) * sizeof(float), "the epoch block lives in the spare floats of ctr");
+static inline EpochBlock* ep_block(float* ctr) { return reinterpret_cast<EpochBlock*>(ctr + EP_BLOCK_OFF); }
 
 int ep_begin(const EpochBlock& B, EpochBlock* dev, hipStream_t s);                                  // *dev = B, cursor = 0
 int ep_end(EpochBlock* dev, const float* losses, int nloss, hipStream_t s);                         // log row `cursor` <- losses; ++cursor
