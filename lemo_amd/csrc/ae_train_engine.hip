@@ -247,16 +247,14 @@ aet_grad_kernel(AeAdamArgs A, float* __restrict__ gpk) {
 // ---------------------------------------------------------------------------------------------------------------------
 // the engine
 // ---------------------------------------------------------------------------------------------------------------------
-struct AetEngine : AeNet {       // (the network's buffers are image 0's; image c's are `c * cs` floats further)
+struct AetEngine : AeNet, TrainReplay {       // (the network's buffers are image 0's; image c's are `c * cs` floats further)
   int bs = 1, groups = 1;
   double lr = 0.0; float lr_f = 0.f, w_body = 10.f, w_v = 10.f, w_c = 1.f;
-  int use_graph = 0, loaded = 0, nblk = 0;
+  int nblk = 0;
   // shared by the batch
   float *theta = nullptr, *m = nullptr, *v = nullptr, *wb = nullptr, *dbp = nullptr, *part = nullptr, *zero_bias = nullptr,
-        *ctr = nullptr, *amax = nullptr, *gpk = nullptr, *lpart = nullptr, *losses = nullptr, *ybuf = nullptr;
+        *amax = nullptr, *gpk = nullptr, *lpart = nullptr, *ybuf = nullptr;
   size_t cs = 0;
-  hipGraphExec_t exec = nullptr;
-  hipGraphExec_t exec_ep[2] = {nullptr, nullptr};      // one step of an epoch (assemble, step, log): [0] evaluation, [1] training
 };
 
 static bool aet_shape_ok(int H, int W, int bs) {
@@ -386,8 +384,7 @@ void* lemo_aetrain_create(const lemo_aetrain_desc* d) {
 void lemo_aetrain_destroy(void* h) {
   AetEngine* e = (AetEngine*)h;
   if (!e) return;
-  destroy_graphs(&e->exec, 1);
-  destroy_graphs(e->exec_ep, 2);
+  e->destroy_graphs();
   delete e;
 }
 
@@ -410,14 +407,7 @@ int lemo_aetrain_step(void* h, const float* x, const float* y, int n, float* los
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   CHK(aet_stage(e, x, y, s));
-  for (int i = 0; i < n; ++i) {
-    if (e->use_graph) {
-      if (!e->exec) CHK(capture_graph(&e->exec, s, false, [&] { return aet_train_step(e, s); }));
-      CHK((int)hipGraphLaunch(e->exec, s));
-    } else {
-      CHK(aet_train_step(e, s));
-    }
-  }
+  CHK(replay_or_run(&e->exec, e->use_graph, n, s, [&] { return aet_train_step(e, s); }));
   if (losses) CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -466,12 +456,7 @@ int lemo_aetrain_epoch(void* h, const lemo_aetrain_epoch_desc* d, void* stream) 
   hipStream_t s = (hipStream_t)stream;
   const bool train = d->train != 0;
   CHK(ep_begin(B, ep_block(e->ctr), s));
-  if (e->use_graph && !e->exec_ep[train]) CHK(capture_graph(&e->exec_ep[train], s, false, [&] { return aet_epoch_step(e, train, s); }));
-  for (int i = 0; i < d->n_steps; ++i) {
-    if (e->use_graph) CHK((int)hipGraphLaunch(e->exec_ep[train], s));
-    else CHK(aet_epoch_step(e, train, s));
-  }
-  return 0;
+  return replay_or_run(&e->exec_ep[train], e->use_graph, d->n_steps, s, [&] { return aet_epoch_step(e, train, s); });
 }
 
 int lemo_aetrain_batch(void* h, const lemo_aetrain_epoch_desc* d, int step, float* x, float* y, void* stream) {

@@ -1,5 +1,5 @@
 // Host-side plumbing every engine shares (lemo_hip.hip, lemo_prox.hip, ae_engine.hip, ae_train_engine.hip, prior_train_engine.hip):
-// the return-on-error macro, stream-capture of a launch sequence into a hipGraphExec, and the release of graph handles.
+// the return-on-error macro, stream-capture of a launch sequence into a hipGraphExec, its replay, and the release of graph handles.
 // Needs nothing but the HIP runtime API and the C ABI's error codes, so tests/capture_helper_main.cpp compiles it against a scripted mock.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +26,15 @@ static int capture_graph(hipGraphExec_t* out, hipStream_t s, bool upload, F&& bo
   if (g) (void)hipGraphDestroy(g);
   if (rc) { *out = nullptr; return rc; }
   if (upload) (void)hipGraphUpload(*out, s);
+  return 0;
+}
+
+// n runs of body() on s.  use_graph: captured once into *exec (kept by the caller across calls; a failed capture leaves it null, so
+// the next call captures again) and launched n times.  Returns the first failure; n <= 0 does nothing.
+template <class F>
+static int replay_or_run(hipGraphExec_t* exec, bool use_graph, int n, hipStream_t s, F&& body) {
+  if (use_graph && !*exec && n > 0) CHK(capture_graph(exec, s, false, body));
+  for (int i = 0; i < n; ++i) CHK(use_graph ? (int)hipGraphLaunch(*exec, s) : body());
   return 0;
 }
 

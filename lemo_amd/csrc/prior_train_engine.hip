@@ -26,20 +26,17 @@ static const int SP_DEC_OUT[10] = {64, 64, 64, 64, 64, 64, 32, 32, 1, 1};
 // packs of its forward and backward-data convolutions (null for the 1-channel layers, which read the flat weights)
 struct SpLayer { int cin, cout, w_off, b_off; float *fwt, *fwt2, *bwt, *bwt2; };
 
-struct SpEngine {
-  int H, W, bs, n_param;
-  double lr;
-  float w_rec, w_smooth;
-  int use_graph, loaded;
-  size_t is, i1;                        // floats per image: CG8P buffer of 64 channels (all CG8P buffers use it) / plain padded image
-  SpLayer enc[10], dec[10];
-  float *theta, *m, *v, *grad, *ctr, *losses, *lpart, *spart, *wsg;
-  float *xin, *x0, *r1, *rec, *drec, *dpre8;
-  float *act[11], *dout[8], *P[3];
-  int nl, nsp;                          // L1 partials (all images), smoothness partials per image
-  SpPackJobs pk;
-  hipGraphExec_t exec;
-  hipGraphExec_t exec_ep[2];            // one step of an epoch (assemble, step, log): [0] evaluation, [1] training
+struct SpEngine : TrainReplay {
+  int H = 0, W = 0, bs = 0, n_param = 0;
+  double lr = 0.0;
+  float w_rec = 0.f, w_smooth = 0.f;
+  size_t is = 0, i1 = 0;                // floats per image: CG8P buffer of 64 channels (all CG8P buffers use it) / plain padded image
+  SpLayer enc[10] = {}, dec[10] = {};
+  float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *lpart = nullptr, *spart = nullptr, *wsg = nullptr;
+  float *xin = nullptr, *x0 = nullptr, *r1 = nullptr, *rec = nullptr, *drec = nullptr, *dpre8 = nullptr;
+  float *act[11] = {}, *dout[8] = {}, *P[3] = {};
+  int nl = 0, nsp = 0;                  // L1 partials (all images), smoothness partials per image
+  SpPackJobs pk = {};
 };
 
 static int sp_layout(SpEngine* e, int H, int W, int bs, float* base, size_t* total) {
@@ -210,8 +207,7 @@ void* lemo_sptrain_create(const lemo_sptrain_desc* d) {
 void lemo_sptrain_destroy(void* h) {
   SpEngine* e = (SpEngine*)h;
   if (!e) return;
-  destroy_graphs(&e->exec, 1);
-  destroy_graphs(e->exec_ep, 2);
+  e->destroy_graphs();
   delete e;
 }
 
@@ -236,14 +232,7 @@ int lemo_sptrain_step(void* h, const float* x, int n, float* losses, void* strea
   if (!e->loaded) return LEMO_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   CHK((int)hipMemcpyAsync(e->xin, x, sizeof(float) * e->bs * e->H * e->W, hipMemcpyDeviceToDevice, s));
-  for (int i = 0; i < n; ++i) {
-    if (e->use_graph) {
-      if (!e->exec) CHK(capture_graph(&e->exec, s, false, [&] { return sp_run(e, s, true); }));
-      CHK((int)hipGraphLaunch(e->exec, s));
-    } else {
-      CHK(sp_run(e, s, true));
-    }
-  }
+  CHK(replay_or_run(&e->exec, e->use_graph, n, s, [&] { return sp_run(e, s, true); }));
   if (losses) CHK((int)hipMemcpyAsync(losses, e->losses, sizeof(float) * 3, hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -284,12 +273,7 @@ int lemo_sptrain_epoch(void* h, const lemo_sptrain_epoch_desc* d, void* stream) 
   hipStream_t s = (hipStream_t)stream;
   const bool train = d->train != 0;
   CHK(ep_begin(B, ep_block(e->ctr), s));
-  if (e->use_graph && !e->exec_ep[train]) CHK(capture_graph(&e->exec_ep[train], s, false, [&] { return sp_epoch_step(e, train, s); }));
-  for (int i = 0; i < d->n_steps; ++i) {
-    if (e->use_graph) CHK((int)hipGraphLaunch(e->exec_ep[train], s));
-    else CHK(sp_epoch_step(e, train, s));
-  }
-  return 0;
+  return replay_or_run(&e->exec_ep[train], e->use_graph, d->n_steps, s, [&] { return sp_epoch_step(e, train, s); });
 }
 
 int lemo_sptrain_batch(void* h, const lemo_sptrain_epoch_desc* d, int step, float* x, void* stream) {

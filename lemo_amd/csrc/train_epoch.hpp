@@ -7,6 +7,16 @@
 
 namespace lemo {
 
+// What both training engines keep next to their networks: the replay state of a step and of an epoch's step, and the two
+// workspace blocks the loop level reads (ctr: Adam's counter + the epoch block below; losses: the last step's loss terms)
+struct TrainReplay {
+  int use_graph = 0, loaded = 0;
+  hipGraphExec_t exec = nullptr;                        // one training step
+  hipGraphExec_t exec_ep[2] = {nullptr, nullptr};       // one step of an epoch (assemble, step, log): [0] evaluation, [1] training
+  float *ctr = nullptr, *losses = nullptr;
+  void destroy_graphs() { lemo::destroy_graphs(&exec, 1); lemo::destroy_graphs(exec_ep, 2); }
+};
+
 // What the kernels of an epoch read from DEVICE memory: the engine keeps one EpochBlock in the spare floats of its `ctr` block
 // (floats EP_BLOCK_OFF .. 63; Adam's counter uses 0 .. 2).  ep_begin writes it once per lemo_*train_epoch call, so a captured
 // step graph carries none of the caller's pointers and is replayed n_steps times with no host patching: the assembly kernel and

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _hip
-from ._engine import release_on_del
+from ._engine import NativeHandle
 from ._hip import ptr
 from .priors import cg8p_alloc, from_cg8p, to_cg8p
 
@@ -423,12 +423,13 @@ class FlatAdam:
             o += p.numel()
 
 
-class _FinetuneSession:
+class _FinetuneSession(NativeHandle):
     """Everything one finetune loop needs, at FIXED device addresses, kept across clips of the same shape: the flat parameter
     leaf and its Adam state, static copies of the clip image and of mask / count, the step's workspace, the stream all of it
     runs on and -- after the first clip -- the captured graph of one training step.  A clip then costs a few small copies
     into the static buffers plus ``steps`` replays; capture + instantiation (~10 ms) is paid once per process and shape,
     not once per clip."""
+    _destroy, _held = 'graph_destroy', ('pool',)
 
     def __init__(self, lib, n_param, x_shape, lr, device):
         self.lib, self.lr, self.device = lib, lr, torch.device(device)
@@ -444,17 +445,11 @@ class _FinetuneSession:
             self.ws = AEWorkspace(self.device)           # the step's ~45 activation buffers: zeroed once, not per step
             self.x = torch.zeros(x_shape, dtype=torch.float32, device=self.device)
             self.moc = torch.zeros(x_shape[-2:], dtype=torch.float32, device=self.device)     # mask / count
-        self.exe, self.pool = None, None
+        self.pool = None                                 # (self.handle: the captured step's graph exec)
 
     def _on(self):
         import contextlib
         return torch.cuda.stream(self.stream) if self.gpu else contextlib.nullcontext()
-
-    def __del__(self, _release=release_on_del):
-        exe, self.exe = getattr(self, 'exe', None), None
-        if exe is not None:
-            lib = self.lib
-            _release(self.device, lib, lambda: lib.graph_destroy(exe))
 
     def train_step(self):
         # loss = (|rec - x| * m).sum() / cnt (opt_amass_temp.py:199-203); its gradient is closed-form, so the eleven small
@@ -475,7 +470,7 @@ class _FinetuneSession:
             self.x.copy_(x); self.moc.copy_(m_over_cnt)
         with self._on():
             left = steps
-            if use_graph and self.exe is None and steps > 3:
+            if use_graph and self.handle is None and steps > 3:
                 for _ in range(3):                           # eager: warms the allocator cache and every lazy init
                     self.train_step()
                 left -= 3
@@ -495,10 +490,10 @@ class _FinetuneSession:
                         exe = C.c_void_p()
                         rc = lib.capture_end(sh, C.byref(exe))
                 lib.check(rc, 'capture_end')
-                self.exe = exe
-            if use_graph and self.exe is not None:
+                self.handle = exe
+            if use_graph and self.handle is not None:
                 for _ in range(left):                        # capture records the step without running it
-                    lib.check(lib.graph_launch(self.exe, self.stream.cuda_stream), 'graph_launch')
+                    lib.check(lib.graph_launch(self.handle, self.stream.cuda_stream), 'graph_launch')
             else:
                 for _ in range(left):
                     self.train_step()
@@ -513,10 +508,11 @@ class _FinetuneSession:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
 
 
-class _EngineSession:
+class _EngineSession(NativeHandle):
     """One clip shape's native finetune engine (``lemo_ae_*``, csrc/ae_engine.hip): the workspace it carves its parameters,
     Adam state, activations and gradients from, its stream, and the output buffers of the eval forward.  Kept across clips
     of the same shape like :class:`_FinetuneSession` (the captured graphs live inside the engine)."""
+    _destroy, _held = 'ae_destroy', ('ws',)              # (the workspace outlives the engine's last launch)
 
     def __init__(self, lib, x_shape, lr, device, clips: int = 1):
         # clips: K clips side by side in every launch (lemo_ae_desc.clips): K workspaces back to back, one engine, one stream
@@ -541,16 +537,7 @@ class _EngineSession:
         self.h = lib.ae_create(C.byref(desc))
         if not self.h:
             raise _hip.LemoHipError('lemo_ae_create failed')
-        self._ev = None
-
-    def __del__(self, _release=release_on_del):
-        h, self.h = getattr(self, 'h', None), None
-        if h:
-            lib = self.lib
-
-            def destroy(h=h, ws=self.ws):                # (the workspace outlives the engine's last launch)
-                lib.ae_destroy(h)
-            _release(self.device, lib, destroy, self._ev)
+        self._run_ev = None                                  # the last run's end: what the release waits for
 
     def _s(self):
         return self.stream.cuda_stream if self.gpu else None
@@ -584,11 +571,11 @@ class _EngineSession:
                 run_on, sh = cur, cur.cuda_stream
             else:
                 self.stream.wait_stream(cur)
-            if self._ev is not None:
+            if self._run_ev is not None:
                 # ALWAYS order the stream about to be used after the session's previous run: a run on caller
                 # stream A followed by a lane / default-stream run used to wait for `cur` only, and ae_load / ae_step then
                 # overwrote the workspace and rec / z / flat that the previous run (or its output clones on A) still used
-                run_on.wait_event(self._ev)
+                run_on.wait_event(self._run_ev)
             _hip.flush_deferred()
         for c, (x, moc) in enumerate(zip(xs, mocs)):
             lib.check(lib.ae_load_clip(self.h, c, ptr(flat0), ptr(x), ptr(moc), sh), 'ae_load_clip')
@@ -597,9 +584,9 @@ class _EngineSession:
             lib.check(lib.ae_forward_clip(self.h, c, ptr(self.rec[c]), ptr(self.z[c]), sh), 'ae_forward_clip')
             lib.check(lib.ae_params_clip(self.h, c, ptr(self.flat[c]), sh), 'ae_params_clip')
         if self.gpu:
-            if self._ev is None:
-                self._ev = torch.cuda.Event()
-            self._ev.record(run_on)
+            if self._run_ev is None:
+                self._run_ev = torch.cuda.Event()
+            self._run_ev.record(run_on)
             if run_on is self.stream:
                 for t in [flat0] + xs + mocs:                # read by the launches above on this session's stream
                     t.record_stream(self.stream)

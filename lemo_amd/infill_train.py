@@ -10,7 +10,6 @@ stay the caller's: the two masking recipes of the reference are the pure torch h
 """
 from __future__ import annotations
 
-import ctypes
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -19,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip
+from ._engine import PriorTrainer
 from ._hip import ptr
 from .infill import _layers
 
@@ -132,46 +132,21 @@ def mask_prox(clip_img: torch.Tensor, mask_clips) -> torch.Tensor:
     return out
 
 
-class InfillPriorTrainer:
+class InfillPriorTrainer(PriorTrainer):
     """AE training steps on the native engine.  ``batch``, ``H``, ``W``: the batch size and the NETWORK input size (d + 2, T + 16:
     210 x 135 for 67 markers and 119 frames).  ``state_dict=None`` starts from ``default_ae_state(seed)``."""
+    _prefix, _nloss, _n_param = 'aetrain', 4, staticmethod(n_param)
+    _masks = None                    # the uploaded PROX masks (upload_prox_masks)
 
     def __init__(self, state_dict: Optional[Dict] = None, batch: int = 60, H: int = 210, W: int = 135, lr: float = 1e-4,
                  weight_loss_rec_body: float = 10., weight_loss_rec_body_v: float = 10., weight_loss_rec_contact_lbl: float = 1.,
                  seed: int = 0, device=None, use_graph: bool = True, _lib=None):
-        self.lib = _lib or _hip.get_lib()
-        if device is None:
-            device = torch.device('cpu') if self.lib.is_emu else torch.device('cuda', torch.cuda.current_device())
-        self.device = torch.device(device)
-        self.bs, self.H, self.W = int(batch), int(H), int(W)
-        self.h = None
-        nws = self.lib.aetrain_ws_floats(self.H, self.W, self.bs)
-        if nws <= 0:
-            raise ValueError(f'infilling-prior training does not take batch {batch} at {H} x {W} '
-                             f'(1 <= batch <= 128, H >= 6, W >= 2, H * W <= 2^22)')
-        self.stream = None if self.lib.is_emu else torch.cuda.Stream(self.device)
-        self.ws = torch.zeros(int(nws), dtype=torch.float32, device=self.device)
-        d = _hip.AetrainDesc(H=self.H, W=self.W, bs=self.bs, lr=float(lr), w_body=float(weight_loss_rec_body),
-                             w_v=float(weight_loss_rec_body_v), w_c=float(weight_loss_rec_contact_lbl), ws=ptr(self.ws),
-                             ws_floats=int(nws), use_graph=int(bool(use_graph) and not self.lib.is_emu))
-        self.h = self.lib.aetrain_create(ctypes.byref(d))
-        if not self.h:
-            raise _hip.LemoHipError('lemo_aetrain_create failed')
-        if state_dict is None:
-            state_dict = default_ae_state(seed)
-        flat = torch.from_numpy(flatten_state(state_dict)).to(self.device)
-        self._losses = torch.zeros(4, dtype=torch.float32, device=self.device)
-        self._call(lambda s: self.lib.check(self.lib.aetrain_load(self.h, ptr(flat), s), 'aetrain_load'))
-
-    def _call(self, fn):
-        if self.stream is None:
-            return fn(None)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        try:
-            return fn(self.stream.cuda_stream)
-        finally:
-            cur.wait_stream(self.stream)
+        super().__init__(_hip.AetrainDesc, batch, H, W, device, use_graph, _lib,
+                         f'infilling-prior training does not take batch {batch} at {H} x {W} '
+                         f'(1 <= batch <= 128, H >= 6, W >= 2, H * W <= 2^22)',
+                         lr=float(lr), w_body=float(weight_loss_rec_body), w_v=float(weight_loss_rec_body_v),
+                         w_c=float(weight_loss_rec_contact_lbl))
+        self._load(flatten_state(default_ae_state(seed) if state_dict is None else state_dict))
 
     def _xy(self, clip_img_input, clip_img, prepared):
         for t in (clip_img_input, clip_img):
@@ -194,7 +169,7 @@ class InfillPriorTrainer:
         """n training steps -> (loss_rec_body, loss_rec_body_v, loss_rec_contact_lbl) of the last step.  prepared=True: the inputs
         are already the padded network input x [bs, 4, H, W] and target y [bs, H, W]"""
         x, y = self._xy(clip_img_input, clip_img, prepared)
-        self._call(lambda s: self.lib.check(self.lib.aetrain_step(self.h, ptr(x), ptr(y), int(n), ptr(self._losses), s), 'aetrain_step'))
+        self._run('step', ptr(x), ptr(y), int(n), ptr(self._losses))
         l = self._losses.cpu()
         return float(l[0]), float(l[1]), float(l[2])
 
@@ -202,7 +177,7 @@ class InfillPriorTrainer:
         """the same losses under the current parameters, no update; return_rec: also the reconstruction [bs, 1, H, W]"""
         x, y = self._xy(clip_img_input, clip_img, prepared)
         rec = torch.empty(self.bs, self.H, self.W, dtype=torch.float32, device=self.device) if return_rec else None
-        self._call(lambda s: self.lib.check(self.lib.aetrain_eval(self.h, ptr(x), ptr(y), ptr(self._losses), ptr(rec), s), 'aetrain_eval'))
+        self._run('eval', ptr(x), ptr(y), ptr(self._losses), ptr(rec))
         l = self._losses.cpu()
         out = (float(l[0]), float(l[1]), float(l[2]))
         return (out + (rec[:, None],)) if return_rec else out
@@ -210,24 +185,13 @@ class InfillPriorTrainer:
     def last_total(self) -> float:
         return float(self._losses[3].cpu())
 
-    def flat_params(self) -> torch.Tensor:
-        out = torch.empty(n_param(), dtype=torch.float32, device=self.device)
-        self._call(lambda s: self.lib.check(self.lib.aetrain_params(self.h, ptr(out), s), 'aetrain_params'))
-        return out.cpu()
-
-    def flat_grads(self) -> torch.Tensor:
-        """the gradient of the last training step (summed over the batch), in the flat order"""
-        out = torch.empty(n_param(), dtype=torch.float32, device=self.device)
-        self._call(lambda s: self.lib.check(self.lib.aetrain_grads(self.h, ptr(out), s), 'aetrain_grads'))
-        return out.cpu()
-
     def pool_winners(self) -> List[torch.Tensor]:
         """the max-pool winners of the five encoder blocks in the last forward: [bs, C, Ho, Wo] uint8 taps ky * 3 + kx each"""
         out, h, w = [], self.H, self.W
         for b, c in enumerate((32, 64, 128, 256, 256)):
             h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
             t = torch.empty(self.bs * c * h * w, dtype=torch.uint8, device=self.device)
-            self._call(lambda s: self.lib.check(self.lib.aetrain_pool_winners(self.h, b, ptr(t), s), 'aetrain_pool_winners'))
+            self._run('pool_winners', b, ptr(t))
             out.append(t.view(self.bs, c // 8, h, w, 8).permute(0, 1, 4, 2, 3).reshape(self.bs, c, h, w).cpu())
         return out
 
@@ -260,28 +224,15 @@ class InfillPriorTrainer:
             raise ValueError(f'mask clips of {m.shape[1]} frames are shorter than the clips ({self.W - 16} frames)')
         self._masks = m.permute(0, 2, 1).contiguous().to(self.device)
 
-    def _index_table(self, t, name, lo, hi, tail=()):
-        t = torch.as_tensor(np.asarray(t) if not torch.is_tensor(t) else t)
-        if t.dtype.is_floating_point or t.dtype == torch.bool:
-            raise ValueError(f'{name} must be an integer tensor')
-        t = t.cpu().long()
-        if t.dim() != 2 + len(tail) or t.shape[1] != self.bs or tuple(t.shape[2:]) != tuple(tail) or t.shape[0] < 1:
-            raise ValueError(f'{name}: expected [n_steps, {self.bs}{"".join(", %d" % v for v in tail)}], got {tuple(t.shape)}')
-        if int(t.min()) < lo or int(t.max()) >= hi:
-            raise ValueError(f'{name} holds values outside [{lo}, {hi})')
-        return t.to(torch.int32).contiguous()
-
-    def _epoch_desc(self, idx, marker_ids, mask_idx):
+    def _epoch_desc(self, idx, marker_ids=None, mask_idx=None):
         """validates every index on the host (nothing has been launched when it raises) -> (descriptor, the tensors it points into)"""
-        if getattr(self, '_data', None) is None:
-            raise ValueError('upload_dataset first')
+        data = self._dataset()
         if marker_ids is not None and mask_idx is not None:
             raise ValueError('one masking recipe per call: marker_ids (random markers) or mask_idx (PROX masks)')
-        idx = self._index_table(idx, 'idx', 0, self._data.shape[0])
+        idx = self._index_table(idx, 'idx', 0, data.shape[0])
         n_steps = idx.shape[0]
         keep = [idx.to(self.device)]
-        d = _hip.AetrainEpochDesc(data=ptr(self._data), n_clips=int(self._data.shape[0]), idx=ptr(keep[0]), n_steps=n_steps,
-                                  recipe=_hip.MASK_NONE)
+        d = _hip.AetrainEpochDesc(data=ptr(data), n_clips=int(data.shape[0]), idx=ptr(keep[0]), n_steps=n_steps, recipe=_hip.MASK_NONE)
         if marker_ids is not None or mask_idx is not None:
             if self.H - 2 != 208:
                 raise ValueError(f'the masking recipes are defined for 67 markers (d = 208), the trainer has d = {self.H - 2}')
@@ -295,7 +246,7 @@ class InfillPriorTrainer:
             keep.append(ids.to(self.device))
             d.recipe, d.marker_ids = _hip.MASK_RANDOM, ptr(keep[-1])
         if mask_idx is not None:
-            if getattr(self, '_masks', None) is None:
+            if self._masks is None:
                 raise ValueError('upload_prox_masks first')
             mi = self._index_table(mask_idx, 'mask_idx', 0, self._masks.shape[0])
             if mi.shape[0] != n_steps:
@@ -305,57 +256,18 @@ class InfillPriorTrainer:
                                                                     int(self._masks.shape[2]), ptr(keep[-1]))
         return d, keep
 
-    def _epoch(self, idx, marker_ids, mask_idx, train):
-        d, keep = self._epoch_desc(idx, marker_ids, mask_idx)
-        log = torch.zeros(d.n_steps, 4, dtype=torch.float32, device=self.device)
-        d.log, d.train = ptr(log), int(train)
-        self._call(lambda s: self.lib.check(self.lib.aetrain_epoch(self.h, ctypes.byref(d), s), 'aetrain_epoch'))
-        out = log.cpu()                                                        # the epoch's one host wait (keeps `keep` alive until then)
-        del keep
-        return out
-
     def fit_epoch(self, idx, marker_ids=None, mask_idx=None) -> torch.Tensor:
         """one training step per row of idx [n_steps, bs] (clips of the uploaded dataset), masked by marker_ids [n_steps, bs, <= 6]
         (random markers, -1 = unused slot) or mask_idx [n_steps, bs] (uploaded PROX masks) or not at all; the batches are
         assembled on the device and the host does not wait between steps.  -> the loss log [n_steps, 4] on the CPU, rows
         (loss_rec_body, loss_rec_body_v, loss_rec_contact_lbl, weighted total).  The RNG stays the caller's."""
-        return self._epoch(idx, marker_ids, mask_idx, True)
+        return self._epoch(*self._epoch_desc(idx, marker_ids, mask_idx), True)
 
     def evaluate_epoch(self, idx, marker_ids=None, mask_idx=None) -> torch.Tensor:
         """the same batches and log under the current parameters, no update (the reference's test-loss loop; average the rows)"""
-        return self._epoch(idx, marker_ids, mask_idx, False)
+        return self._epoch(*self._epoch_desc(idx, marker_ids, mask_idx), False)
 
     def assemble(self, step: int, idx, marker_ids=None, mask_idx=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """the batch of row `step` as the epoch kernels build it: (x [bs, 4, H, W], y [bs, H, W]) on the trainer's device"""
-        d, keep = self._epoch_desc(idx, marker_ids, mask_idx)
-        if not 0 <= int(step) < d.n_steps:
-            raise ValueError(f'step {step} outside [0, {d.n_steps})')
-        x = torch.empty(self.bs, 4, self.H, self.W, dtype=torch.float32, device=self.device)
-        y = torch.empty(self.bs, self.H, self.W, dtype=torch.float32, device=self.device)
-        self._call(lambda s: self.lib.check(self.lib.aetrain_batch(self.h, ctypes.byref(d), int(step), ptr(x), ptr(y), s), 'aetrain_batch'))
-        _hip.quiesce(self.device, self.lib)                                    # the index tables are released on return
+        x, y = self._assemble(*self._epoch_desc(idx, marker_ids, mask_idx), step, (self.bs, 4, self.H, self.W), (self.bs, self.H, self.W))
         return x, y
-
-    def save_state(self) -> torch.Tensor:
-        """parameters, both Adam moments and the step counter as one flat CPU tensor (include/lemo_hip.h has the layout)"""
-        out = torch.empty(int(self.lib.aetrain_state_floats()), dtype=torch.float32, device=self.device)
-        self._call(lambda s: self.lib.check(self.lib.aetrain_state_save(self.h, ptr(out), s), 'aetrain_state_save'))
-        return out.cpu()
-
-    def load_state(self, blob: torch.Tensor) -> None:
-        """restore what save_state returned: training continues bit-identically"""
-        n = int(self.lib.aetrain_state_floats())
-        if not torch.is_tensor(blob) or blob.dtype != torch.float32 or blob.dim() != 1 or blob.numel() != n:
-            raise ValueError(f'a training state is a flat float32 tensor of {n} values')
-        t = blob.to(self.device).contiguous()
-        self._call(lambda s: self.lib.check(self.lib.aetrain_state_load(self.h, ptr(t), s), 'aetrain_state_load'))
-        _hip.quiesce(self.device, self.lib)
-
-    def close(self):
-        if getattr(self, 'h', None):
-            _hip.quiesce(self.device, self.lib)
-            self.lib.aetrain_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()

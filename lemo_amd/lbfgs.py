@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from ._engine import release_on_del
+from ._engine import NativeHandle
 
 DIRECTION, EVAL, DONE = 0, 1, 2
 PHASES = ('initial', 'bracket', 'zoom')
@@ -344,10 +344,11 @@ class LBFGSLs(torch.optim.Optimizer):
         return loss0
 
 
-class NativeLBFGS:
+class NativeLBFGS(NativeHandle):
     """``lemo_lbfgs_*`` over a workspace this object allocates with torch.  ``begin(x, g, f)`` / ``ask()`` / ``tell(g, f)`` with
     device tensors (``f``: a float32 tensor of one element).  ``ask`` returns ``(EVAL, x_trial)`` or ``(DONE, x_accepted)``; ``ask``
     and ``tell`` wait for the current stream."""
+    _destroy, _held = 'lbfgs_destroy', ('ws',)
 
     def __init__(self, n: int, device, lr=1.0, max_iter=20, max_eval=None, tolerance_grad=1e-5, tolerance_change=1e-9, history_size=100,
                  c1=1e-4, c2=0.9, max_ls=25, _lib=None):
@@ -366,15 +367,6 @@ class NativeLBFGS:
             raise ValueError('NativeLBFGS: lemo_lbfgs_create refused the options (lr, c1, c2 and the tolerances must be positive and finite)')
         self.x_trial = torch.zeros(self.n, dtype=torch.float32, device=self.device)
         self._logs = None
-
-    def __del__(self, _release=release_on_del):
-        h, self.handle = getattr(self, 'handle', None), None
-        if h:
-            destroy = self.lib.lbfgs_destroy
-            _release(self.device, self.lib, lambda: destroy(h))
-
-    def _s(self):
-        return self.lib.stream(self.device)
 
     def log(self, rows: int):
         """keep the point and the direction of the next ``rows`` evaluations (diagnostics) -> (xlog, dlog) [rows, n]"""

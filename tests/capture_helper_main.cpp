@@ -1,4 +1,4 @@
-// Stand-alone check of lemo::capture_graph / lemo::destroy_graphs (lemo_amd/csrc/engine_host.hpp) against the scripted runtime in
+// Stand-alone check of lemo::capture_graph / lemo::replay_or_run / lemo::destroy_graphs (lemo_amd/csrc/engine_host.hpp) against the scripted runtime in
 // tests/capture_mock: the error paths no GPU test can reach.  Built and run by tests/test_capture_helper.py with
 // -fsanitize=address,undefined, so a graph destroyed twice or leaked fails the run as well.  Prints one line per case; exit 0 = all hold.
 #include "engine_host.hpp"
@@ -27,6 +27,55 @@ static Run run(Call fail_call, int code, int body_rc, bool upload, bool graph_on
   EXPECT(!st().capturing);
   EXPECT(st().count(GRAPH_DESTROY) <= 1);
   return r;
+}
+
+// lemo::replay_or_run: what the training engines' step and epoch loops are made of
+static void replay_cases() {
+  int bodies = 0, body_rc = 0;
+  auto body = [&] { ++bodies; return body_rc; };
+  auto captures = [] { return st().count(BEGIN) + st().count(END) + st().count(INSTANTIATE); };
+  hipGraphExec_t exec = nullptr;
+
+  std::printf("replay, eager: n bodies, no capture call\n");
+  st() = State();
+  EXPECT(lemo::replay_or_run(&exec, false, 3, nullptr, body) == 0);
+  EXPECT(bodies == 3 && exec == nullptr && st().log.empty());
+
+  std::printf("replay, eager: the first body failure ends the loop\n");
+  bodies = 0; body_rc = LEMO_ERR_SHAPE;
+  EXPECT(lemo::replay_or_run(&exec, false, 3, nullptr, body) == LEMO_ERR_SHAPE && bodies == 1 && st().log.empty());
+
+  std::printf("replay, graph, n = 0: no capture\n");
+  bodies = 0; body_rc = 0;
+  EXPECT(lemo::replay_or_run(&exec, true, 0, nullptr, body) == 0);
+  EXPECT(bodies == 0 && exec == nullptr && st().log.empty());
+
+  std::printf("replay, graph: a body failure inside the capture is returned, nothing is launched, the next call captures again\n");
+  body_rc = LEMO_ERR_ARG;
+  EXPECT(lemo::replay_or_run(&exec, true, 2, nullptr, body) == LEMO_ERR_ARG);
+  EXPECT(bodies == 1 && exec == nullptr && !st().capturing);
+  EXPECT(st().count(BEGIN) == 1 && st().count(END) == 1 && st().count(INSTANTIATE) == 0 && st().count(LAUNCH) == 0);
+
+  std::printf("replay, graph, first call: one begin / end / instantiate, n launches\n");
+  st() = State();
+  bodies = 0; body_rc = 0;
+  EXPECT(lemo::replay_or_run(&exec, true, 3, nullptr, body) == 0);
+  EXPECT(bodies == 1 && exec != nullptr && captures() == 3 && st().count(UPLOAD) == 0 && st().count(LAUNCH) == 3);
+  const int order[7] = {BEGIN, END, INSTANTIATE, GRAPH_DESTROY, LAUNCH, LAUNCH, LAUNCH};
+  EXPECT((int)st().log.size() == 7 && std::memcmp(st().log.data(), order, sizeof(order)) == 0);
+
+  std::printf("replay, graph, second call: no capture, n launches\n");
+  st() = State();
+  const hipGraphExec_t kept = exec;
+  EXPECT(lemo::replay_or_run(&exec, true, 2, nullptr, body) == 0);
+  EXPECT(bodies == 1 && exec == kept && captures() == 0 && st().count(LAUNCH) == 2 && st().log.size() == 2);
+
+  std::printf("replay, graph: a launch failure is returned at once, the graph is kept\n");
+  st() = State();
+  st().fail[LAUNCH] = 17;
+  EXPECT(lemo::replay_or_run(&exec, true, 3, nullptr, body) == 17);
+  EXPECT(bodies == 1 && exec == kept && st().count(LAUNCH) == 1 && st().log.size() == 1);
+  lemo::destroy_graphs(&exec, 1);
 }
 
 int main() {
@@ -78,6 +127,7 @@ int main() {
     EXPECT(r.rc == 0 && r.out != nullptr);
     lemo::destroy_graphs(&r.out, 1);
   }
+  replay_cases();
   std::printf(failures ? "%d checks failed\n" : "all capture_graph checks hold\n", failures);
   return failures ? 1 : 0;
 }

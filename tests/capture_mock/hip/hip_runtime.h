@@ -1,4 +1,4 @@
-// Scripted mock of the six HIP runtime calls lemo_amd/csrc/engine_host.hpp makes, for tests/capture_helper_main.cpp: every call is
+// Scripted mock of the seven HIP runtime calls lemo_amd/csrc/engine_host.hpp makes, for tests/capture_helper_main.cpp: every call is
 // recorded in mock::log, and a call fails with mock::fail[call] when that is non-zero.  Graphs and execs are heap blocks, so the
 // address sanitizer reports a graph destroyed twice or never.
 #pragma once
@@ -15,7 +15,7 @@ typedef mockExec* hipGraphExec_t;
 enum hipStreamCaptureMode { hipStreamCaptureModeGlobal, hipStreamCaptureModeThreadLocal, hipStreamCaptureModeRelaxed };
 
 namespace mock {
-enum Call { BEGIN, END, INSTANTIATE, UPLOAD, GRAPH_DESTROY, EXEC_DESTROY, NCALL };
+enum Call { BEGIN, END, INSTANTIATE, UPLOAD, GRAPH_DESTROY, EXEC_DESTROY, LAUNCH, NCALL };
 struct State {
   int fail[NCALL] = {};
   std::vector<int> log;
@@ -58,4 +58,8 @@ inline hipError_t hipGraphExecDestroy(hipGraphExec_t x) {
   mock::note(mock::EXEC_DESTROY);
   delete x;
   return hipSuccess;
+}
+inline hipError_t hipGraphLaunch(hipGraphExec_t x, hipStream_t) {
+  const int e = mock::note(mock::LAUNCH);
+  return (x && x->alive && !mock::st().capturing) ? e : 1;
 }

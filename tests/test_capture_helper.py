@@ -1,5 +1,5 @@
-"""Contract of the engines' stream-capture helper (lemo_amd/csrc/engine_host.hpp: capture_graph, destroy_graphs) on its error
-paths -- begin / body / end / instantiate failing, upload on and off -- which no GPU test can reach without provoking a fault.
+"""Contract of the engines' stream-capture helper (lemo_amd/csrc/engine_host.hpp: capture_graph, replay_or_run, destroy_graphs) on its error
+paths -- begin / body / end / instantiate / launch failing, upload on and off, capture once then replay -- which no GPU test can reach without provoking a fault.
 tests/capture_helper_main.cpp drives the header against the scripted runtime of tests/capture_mock as a stand-alone host program
 under the address and undefined-behaviour sanitizers (a graph destroyed twice or leaked ends the run with an error)."""
 import os

@@ -52,6 +52,38 @@ def test_bad_indices_are_refused_on_the_host(emu_lib):
     E.check_bad_indices_are_refused(emu_lib, CPU)
 
 
+def test_smoothness_trainer_refuses_bad_index_tables_before_any_launch(emu_lib, monkeypatch):
+    """float, bool, wrong-rank, wrong-width, empty and out-of-range idx raise ValueError from the trainers' shared _index_table, with
+    its messages, and neither lemo_sptrain_epoch nor lemo_sptrain_batch has been called by then"""
+    from lemo_amd._engine import PriorTrainer
+    from lemo_amd.infill_train import InfillPriorTrainer
+    from lemo_amd.smooth_train import SmoothPriorTrainer
+    assert SmoothPriorTrainer._index_table is PriorTrainer._index_table is InfillPriorTrainer._index_table
+    st = E.sp_trainer(emu_lib, CPU, False, clips=E.sp_clips())
+    calls = []
+    for name in ('sptrain_epoch', 'sptrain_batch'):
+        monkeypatch.setattr(emu_lib, name, lambda *a, _n=name: calls.append(_n) or 0)
+    ok = E.SP_IDX[:2]
+    high, low = ok.clone(), ok.clone()
+    high[1, 0], low[0, 1] = E.SP_N, -1
+    cases = ((ok.float(), 'idx must be an integer tensor'), (ok.double().numpy(), 'idx must be an integer tensor'),
+             (ok > 0, 'idx must be an integer tensor'), (ok[0], f'idx: expected [n_steps, {E.SP_BS}], got (2,)'),
+             (ok[:, :, None], f'idx: expected [n_steps, {E.SP_BS}], got (2, 2, 1)'), (ok[:, :1], f'idx: expected [n_steps, {E.SP_BS}], got (2, 1)'),
+             (ok[:0], f'idx: expected [n_steps, {E.SP_BS}], got (0, 2)'), (high, f'idx holds values outside [0, {E.SP_N})'),
+             (low, f'idx holds values outside [0, {E.SP_N})'))
+    for fn in (st.fit_epoch, st.evaluate_epoch, lambda i: st.assemble(0, i)):
+        for arg, msg in cases:
+            with pytest.raises(ValueError) as err:
+                fn(arg)
+            assert str(err.value) == msg
+    with pytest.raises(ValueError):
+        st.assemble(2, ok)                                                       # a good table, a step past its end
+    assert calls == []
+    monkeypatch.undo()
+    assert st.fit_epoch(ok.int().numpy()).shape == (2, 3)                        # a good table in another integer type still runs
+    st.close()
+
+
 def test_upload_prox_masks_takes_both_layouts(emu_lib, ae_data):
     clips, masks = ae_data
     tr = E.ae_trainer(emu_lib, CPU, False, clips=clips)

@@ -1,6 +1,9 @@
 """GPU suite: the loop level of the training engines on an MI355X (tests/train_epoch_common.py has the cases, shared with the
 emulator suite): assembly bit for bit against the torch recipes, an epoch (eager and as a replayed graph) against the eager loop
 of step() calls it replaces, the checkpoint, and one case of each engine at the shipped image shape."""
+import gc
+import weakref
+
 import pytest
 import torch
 
@@ -51,6 +54,33 @@ def test_smoothness_checkpoint_resumes_bit_identically(gpu):
 
 def test_bad_indices_are_refused_on_the_host(gpu):
     E.check_bad_indices_are_refused(*gpu)
+
+
+def test_close_during_a_capture_parks_the_destroy(gpu, monkeypatch):
+    """close() while some stream is being captured (pretended here: no capture is started) must not destroy the engine under it:
+    the destroy is parked with the workspace, h is None at once, a second close() does nothing, and the first flush after the
+    capture runs the destroy exactly once"""
+    lib, dev = gpu
+    tr = E.sp_trainer(lib, dev, False)
+    torch.cuda.synchronize(dev)
+    _hip.flush_deferred()
+    destroyed, real = [], lib.sptrain_destroy
+    monkeypatch.setattr(lib, 'sptrain_destroy', lambda h: destroyed.append(h) or real(h))
+    n0, ws = len(_hip._DEFERRED), weakref.ref(tr.ws)
+    with monkeypatch.context() as m:
+        m.setattr(torch.cuda, 'is_current_stream_capturing', lambda: True)
+        tr.close()
+        assert destroyed == [] and len(_hip._DEFERRED) == n0 + 1 and tr.h is None
+        tr.close()
+        assert destroyed == [] and len(_hip._DEFERRED) == n0 + 1
+        del tr                                                                   # the trainer goes: the parked destroy holds the workspace
+        gc.collect()
+        _hip.flush_deferred()                                                    # still "capturing": stays parked
+        assert destroyed == [] and len(_hip._DEFERRED) == n0 + 1 and ws() is not None
+    _hip.flush_deferred()
+    assert len(destroyed) == 1 and len(_hip._DEFERRED) == n0 and ws() is None
+    _hip.flush_deferred()
+    assert len(destroyed) == 1
 
 
 def test_a_second_epoch_replays_the_captured_step_with_new_tables(gpu, ae_data):
