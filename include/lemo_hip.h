@@ -134,6 +134,26 @@ int lemo_vposer_decode_bwd(const lemo_vposer_w* w, const float* h1, const float*
 /* MLP part of the VPoser backward alone: dout [B][128] (= scratch[0 .. B*128)) -> dz */
 int lemo_vposer_mlp_bwd(const lemo_vposer_w* w, const float* h1, const float* h2, int B, float* dz, int dz_stride,
                         float* scratch, void* stream);
+/* ---- VPoser.encode in eval mode, human_body_prior/train/vposer_smpl.py:98-105, forward and input gradient (csrc/vposer_enc_kernels.hip)
+ * x [B][63] -> bn1 -> fc1 -> lrelu -> bn2 -> fc2 -> lrelu -> mean = mu(h2), std = softplus(logvar(h2)).  BatchNorm (running statistics,
+ * eps 1e-5) is folded into the next layer on the host, in float64: fc1' = fc1 diag(s1), b1' = b1 + fc1 t1 with s = gain / sqrt(var + eps),
+ * t = shift - mean s; fc2' likewise with bn2.  The two heads are one [64][512] layer: mu rows 0..31, logvar rows 32..63. */
+typedef struct lemo_vposer_enc_w {       /* *p = fragment-order pack P[K/16][M/16][64][4] of a row-major [M][K] matrix: lane 16 q + i of
+                                          * (chunk c, tile mt) holds W[16 mt + i][16 c + 4 q .. + 3]; *tp = the same pack of the transpose */
+  const float *w1p, *w1tp, *b1;          /* bn1 + bodyprior_enc_fc1  [512][64] (column 63 zero) / [64][512] (row 63 zero) / [512] */
+  const float *w2p, *w2tp, *b2;          /* bn2 + bodyprior_enc_fc2  [512][512] / [512][512] / [512] */
+  const float *whp, *whtp, *bh;          /* bodyprior_enc_mu | bodyprior_enc_logvar  [64][512] / [512][64] / [64] */
+} lemo_vposer_enc_w;
+/* pin: B rows of 63 floats, pin_stride >= 63 floats apart (column 63 is never read); mean, std: B rows of 32, out_stride >= 32 apart; nothing
+ * outside those columns is read or written.  h1, h2 [B][512] and lv [B][32] (the pre-softplus logvar output), 16-byte aligned, are what the
+ * backward needs; each may be NULL (not saved).  LEMO_ERR_ARG, nothing written: B <= 0, a null w / pin / mean / std, pin_stride < 63,
+ * out_stride < 32. */
+int lemo_vposer_encode_fwd(const lemo_vposer_enc_w* w, const float* pin, int pin_stride, int B, float* mean, float* std, int out_stride,
+                           float* h1, float* h2, float* lv, void* stream);
+/* d_mean, d_std: B rows of 32, out_stride apart; either may be NULL (= zero).  dpin: B rows of 63 written, pin_stride apart.  LEMO_ERR_ARG,
+ * nothing written: B <= 0, a null w / h1 / h2 / lv / dpin, pin_stride < 63, out_stride < 32.  Parameter gradients are not computed. */
+int lemo_vposer_encode_bwd(const lemo_vposer_enc_w* w, const float* h1, const float* h2, const float* lv, const float* d_mean,
+                           const float* d_std, int out_stride, int B, float* dpin, int pin_stride, void* stream);
 /* generic small NT GEMM on the matrix cores: C[n][m] = epi(sum_k A[m][k] B[n][k]); M, K multiples of 16 */
 int lemo_gemm_nt16(const float* A, int lda, const float* B, int ldb, int M, int N, int K, float* C, int ldc,
                    const float* bias, const float* aux, int ldaux, int epi, void* stream);

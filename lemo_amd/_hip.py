@@ -27,6 +27,11 @@ class VPoserW(C.Structure):
     _fields_ = [(n, vp) for n in ('w1', 'w1t', 'b1', 'w2', 'w2t', 'b2', 'w3', 'w3t', 'b3')]
 
 
+class VPoserEncW(C.Structure):
+    """lemo_vposer_enc_w: the BatchNorm-folded encoder in fragment order, both orientations (lemo_amd.vposer.pack_vposer_enc)"""
+    _fields_ = [(n, vp) for n in ('w1p', 'w1tp', 'b1', 'w2p', 'w2tp', 'b2', 'whp', 'whtp', 'bh')]
+
+
 class BodyConst(C.Structure):
     _fields_ = [('nj', C.c_int), ('nshape', C.c_int), ('ncomp', C.c_int), ('nlev', C.c_int)] + \
         [(n, vp) for n in ('parents', 'level_start', 'level_joints', 'child_start', 'child_list',
@@ -289,6 +294,8 @@ _SIGS = {
     'lemo_vposer_decode_fwd': (C.c_int, [C.POINTER(VPoserW), vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     'lemo_vposer_decode_bwd': (C.c_int, [C.POINTER(VPoserW), vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp]),
     'lemo_vposer_mlp_bwd': (C.c_int, [C.POINTER(VPoserW), vp, vp, C.c_int, vp, C.c_int, vp, vp]),
+    'lemo_vposer_encode_fwd': (C.c_int, [C.POINTER(VPoserEncW), vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    'lemo_vposer_encode_bwd': (C.c_int, [C.POINTER(VPoserEncW), vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]),
     'lemo_gemm_nt16': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp]),
     'lemo_gemm_nt16_splitk_part_floats': (C.c_int, [C.c_int, C.c_int]),
     'lemo_gemm_nt16_splitk': (C.c_int, [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp]),

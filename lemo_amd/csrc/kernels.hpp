@@ -176,6 +176,15 @@ static inline float* vposer_scratch_dh1(float* scratch, int B) { return scratch 
 int vposer_mlp_bwd(const VPoserW& w, const float* h1, const float* h2, int B, float* dz, int dz_stride, float* scratch,
                    hipStream_t s);
 int rot6d_to_aa_fwd(const float* x6, int stride, int N, float* aa, hipStream_t s);
+// ---------------- vposer_enc_kernels.hip ----------------
+typedef lemo_vposer_enc_w VPoserEncW;
+// the eval-mode encoder, one launch: saves h1, h2 [B][512], lv [B][32] where given
+int vposer_encode_fwd(const VPoserEncW& w, const float* pin, int pin_stride, int B, float* mean, float* stdv, int out_stride,
+                      float* h1, float* h2, float* lv, hipStream_t s);
+// d_mean and / or d_std (null = zero) -> dpin [B] rows of 63 with stride pin_stride, one launch
+int vposer_encode_bwd(const VPoserEncW& w, const float* h1, const float* h2, const float* lv, const float* d_mean, const float* d_std,
+                      int out_stride, int B, float* dpin, int pin_stride, hipStream_t s);
+
 int rot6d_to_aa_bwd(const float* x6, int stride, const float* d_aa, int N, float* dx6, hipStream_t s);
 int smplx_pose_fwd(const BodyConst& c, const PoseIn& in, const PoseWs& ws, int B, hipStream_t s);
 int smplx_pose_bwd(const BodyConst& c, const PoseWs& ws, const PoseGradIn& gi, const PoseGradOut& go, int B, hipStream_t s);

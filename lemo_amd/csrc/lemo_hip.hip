@@ -143,6 +143,16 @@ int lemo_vposer_mlp_bwd(const lemo_vposer_w* w, const float* h1, const float* h2
   if (!w || !h1 || !h2 || !dz || !scratch) return LEMO_ERR_ARG;
   return vposer_mlp_bwd(*w, h1, h2, B, dz, dz_stride, scratch, S(stream));
 }
+int lemo_vposer_encode_fwd(const lemo_vposer_enc_w* w, const float* pin, int pin_stride, int B, float* mean, float* std, int out_stride,
+                           float* h1, float* h2, float* lv, void* stream) {
+  if (!w) return LEMO_ERR_ARG;
+  return vposer_encode_fwd(*w, pin, pin_stride, B, mean, std, out_stride, h1, h2, lv, S(stream));
+}
+int lemo_vposer_encode_bwd(const lemo_vposer_enc_w* w, const float* h1, const float* h2, const float* lv, const float* d_mean,
+                           const float* d_std, int out_stride, int B, float* dpin, int pin_stride, void* stream) {
+  if (!w) return LEMO_ERR_ARG;
+  return vposer_encode_bwd(*w, h1, h2, lv, d_mean, d_std, out_stride, B, dpin, pin_stride, S(stream));
+}
 int lemo_gemm_nt16(const float* A, int lda, const float* B, int ldb, int M, int N, int K, float* C, int ldc,
                    const float* bias, const float* aux, int ldaux, int epi, void* stream) {
   if (!A || !B || !C) return LEMO_ERR_ARG;

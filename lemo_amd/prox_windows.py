@@ -118,6 +118,23 @@ def window_start_params(init: Mapping[str, np.ndarray]) -> Dict[str, np.ndarray]
     return out
 
 
+def with_pose_embedding(params: Mapping[str, np.ndarray], vposer) -> Mapping[str, np.ndarray]:
+    """a window's parameter dict with ``pose_embedding`` in it: ``params`` itself when it has one, else a copy in which it is the
+    VPoser encoder's mean of ``body_pose`` ([B, 63]; :func:`lemo_amd.vposer.embed_body_pose`) -- so a window can start from any
+    SMPL-X pose estimate, not only from results that store the latent"""
+    if params.get('pose_embedding') is not None:
+        return params
+    import torch
+    from .vposer import embed_body_pose
+    bp = np.asarray(params['body_pose'], np.float32)
+    dev = vposer.bodyprior_enc_fc1.weight.device
+    with torch.no_grad():
+        emb, _ = embed_body_pose(vposer, torch.from_numpy(bp.reshape(bp.shape[0], -1)).to(dev))
+    out = dict(params)
+    out['pose_embedding'] = emb.cpu().numpy()
+    return out
+
+
 def run_recording(frame_names: Sequence[str], batch_size: int, current_dir: str, prox_dir: str, fit_window,
                   reference_chunking: bool = False) -> int:
     """drive ``fit_window(frame_names, init_params, first_window, n_frozen) -> (camera_params, body_params,
